@@ -1,8 +1,16 @@
 #!/usr/bin/env python
 """Benchmark: env-steps/s of the Learner hot path (rollout + learn) on N MI355X, weak scaling.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5|c1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5|c1] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K updates and prints the result line (the headline rate,
+``ms_per_step``, the per-phase times of the timed updates and the algorithmic total roofline).
+``--full`` adds everything that takes runs of its own: the probed pass behind the two kernel
+rooflines, the PPO loss delta against the CPU restatement (one more update) and the CPU baselines;
+``--no-roofline`` / ``--no-loss-delta`` / ``--no-cpu-baseline`` drop single parts of a full run.
+``--dump-outputs DIR`` writes what the last timed update returned (trajectory, episode lengths,
+returns, updated weights) as DIR/<name>.npy (dump_outputs).
 
 ``--gpus N`` with N > 1 and no launcher around it (no WORLD_SIZE) starts the N ranks itself:
 this script re-runs under ``torch.distributed.run`` as a child process (launch_ranks) before the
@@ -14,10 +22,10 @@ minibatches of PPO/world-model updates with clip + AdoptAtan2 + EMA).  Inputs ar
 (Philox LunarLander-shaped VecSim) and weights random-init; the timed region contains whole
 updates only (no checkpoint writes).
 
-Printed (rank 0, one JSON line): BASELINE metric + roofline of the decode-attention kernel
-(HIP events around every launch in the timed region) + the CPU baseline (the oracle's batch-1
-restatement of the reference Learner timed on this host) + the PPO loss delta vs that CPU
-reference on identical weights and minibatch.
+Printed (rank 0, one JSON line): BASELINE metric; with ``--full`` also the rooflines of the
+decode-attention and weight-gradient kernels (HIP events around every launch of a probed pass), the
+CPU baseline (the oracle's batch-1 restatement of the reference Learner timed on this host) and the
+PPO loss delta vs that CPU reference on identical weights and minibatch.
 """
 from __future__ import annotations
 
@@ -184,6 +192,8 @@ def build_learner(cfg, seed, use_graph=True, world=1):
 
 PHASES = []   # (start, after rollout, after learn) events of the timed updates
 HOST_TIMES = {}   # host envs: seconds of the timed updates' steps in decode (+ wait) / env step / feedback
+LAST = {}     # what the latest update's rollout returned (references only; --dump-outputs reads them)
+DUMP_BUDGET = 64 << 20   # bytes --dump-outputs may write in all
 
 
 def one_update(learner, env, T, probe=None, phases=False):
@@ -210,7 +220,67 @@ def one_update(learner, env, T, probe=None, phases=False):
         ev[2].record()
         PHASES.append(ev)
     agent.logs = []
+    LAST.update(traj=traj, lens=lens, cum=cum)
     return steps, lens
+
+
+def dump_outputs(out_dir, learner, seed):
+    """--dump-outputs: what the last timed update handed back to its caller, as <name>.npy (float32;
+    float64 for indices and counts), at most DUMP_BUDGET bytes in all.
+
+    * ``traj_<key>`` — the rollout's trajectory tensors (states, actions, logp, rewards, bounds, values)
+      of a sample of its episodes, positions past an episode's end zeroed (the buffers keep earlier
+      rollouts there); ``episodes`` holds the sampled episode indices (sorted; all of them when they
+      fit a third of the budget), ``lens`` / ``cum_reward`` every episode's length and return.
+    * ``params`` / ``ema_params`` — the flat weight vector after the update's optimiser steps and its
+      EMA (the rollout policy), or the elements ``param_index`` of both when the two do not fit half
+      the budget; ``rs_mean`` / ``rs_var`` — the RSNorm state.
+
+    The samples are drawn by numpy's generator seeded with ``--seed``, so they are the same from run
+    to run and from build to build."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    agent = learner.agent
+    traj = {k: v for k, v in LAST['traj'].items() if torch.is_tensor(v)}
+    lens = LAST['lens'].detach().cpu().long()
+    E = lens.numel()
+    per_episode = sum(v[0].numel() for v in traj.values()) * 4
+    n_ep = max(1, min(E, (DUMP_BUDGET // 3) // max(per_episode, 1)))
+    episodes = torch.from_numpy(np.sort(rng.choice(E, size=n_ep, replace=False))) if n_ep < E else torch.arange(E)
+    written = 0
+
+    def save(name, t, dtype=np.float32):
+        nonlocal written
+        a = np.ascontiguousarray(t.detach().cpu().numpy().astype(dtype))
+        written += a.nbytes
+        if written > DUMP_BUDGET:
+            raise RuntimeError(f'--dump-outputs: {name} takes the dump past {DUMP_BUDGET} bytes')
+        np.save(out_dir / f'{name}.npy', a)
+
+    save('episodes', episodes, np.float64)
+    save('lens', lens, np.float64)
+    save('cum_reward', LAST['cum'])
+    for k, v in traj.items():
+        rows = v[:E].index_select(0, episodes.to(v.device)).float()
+        if rows.ndim == 1:   # per-episode values (the host rollout's bootstrap value, NaN = none -> 0)
+            save(f'traj_{k}', rows.nan_to_num(nan=0.))
+            continue
+        valid = torch.arange(rows.shape[1])[None, :] < lens.index_select(0, episodes)[:, None]
+        valid = valid.reshape(valid.shape + (1,) * (rows.ndim - 2)).to(rows.device)
+        save(f'traj_{k}', torch.where(valid, rows, torch.zeros_like(rows)))
+    flat, ema = agent.flat.flat, agent.ema_flat
+    n = flat.numel()
+    if n * 8 > DUMP_BUDGET // 2:   # (4 + 4 bytes of the two vectors and 8 of the index per sampled element)
+        keep = (DUMP_BUDGET // 2) // 16
+        idx = torch.from_numpy(np.sort(rng.choice(n, size=keep, replace=False)))
+        save('param_index', idx, np.float64)
+        flat, ema = flat.index_select(0, idx.to(flat.device)), ema.index_select(0, idx.to(ema.device))
+    save('params', flat)
+    save('ema_params', ema)
+    save('rs_mean', agent.rs_mean)
+    save('rs_var', agent.rs_var)
+    return written
 
 
 class DecodeAttnTimer:
@@ -559,11 +629,17 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--config', default='c3', choices=sorted(CONFIGS))
     ap.add_argument('--seed', type=int, default=0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also the probed roofline pass, the PPO loss delta and the CPU baselines (runs of their own)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed update returned as DIR/<name>.npy (see dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
     ap.add_argument('--no-graph', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-loss-delta', action='store_true')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the probed roofline pass')
+    ap.add_argument('--no-loss-delta', action='store_true', help='with --full: skip the PPO loss delta')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # no launcher: start the N ranks ourselves (before this process touches the GPU)
@@ -603,7 +679,7 @@ def main():
     # headline region below carries no probe events.
     timer = gtimer = None
     value_probed = None
-    if not args.no_roofline and not host:
+    if args.full and not args.no_roofline and not host:
         timer = DecodeAttnTimer(learner, env, T)
         # capture the rollout graph with the event records inside, and count the weight-gradient
         # launches of one update to size the probed pass's event pool exactly
@@ -649,6 +725,8 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     progress(f'timed: {args.steps} updates in {elapsed:.2f} s')
+    if args.dump_outputs and rank == 0:   # (before anything below runs another update over the buffers)
+        progress(f'dumped {dump_outputs(args.dump_outputs, learner, args.seed)} bytes to {args.dump_outputs}')
     lens_last = lens_last.cpu().numpy() if lens_last is not None else None
     el = torch.tensor([elapsed], device='cuda', dtype=torch.float64)
     if world > 1:
@@ -720,7 +798,7 @@ def main():
     # the loss-delta check runs one more update on EVERY rank (its learn all-reduces gradients; rank 0
     # compares its local first minibatch with the CPU restatement), then the process group ends and
     # rank 0 alone times the CPU baseline, so no rank waits in a collective the others never enter
-    if not (args.no_loss_delta or host):
+    if args.full and not (args.no_loss_delta or host):
         try:
             loss_delta = ppo_loss_delta(learner, env, cfg, check=(rank == 0))
         except Exception as e:   # reported, never hidden
@@ -734,7 +812,7 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, args.seed, 20.)
         phys, share = host_cores()
         one = cpu_baseline(cfg, args.seed, 20., threads=1,

@@ -57,10 +57,27 @@ def load_reference():
     return out
 
 
+PART_BYTES = 880 * 1024   # array bytes per file: every committed fixture file stays under 1 MiB
+
+
 def save(name, **arrays):
+    """<name>.npz, or <name>.part1.npz, <name>.part2.npz, ... (the keys in order) when the arrays
+    take more than PART_BYTES; the tests' ``golden`` fixture reads either form."""
     arrays = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in arrays.items()}
-    np.savez(HERE / f'{name}.npz', **arrays)
-    print(f'wrote {name}.npz  ({sum(a.nbytes for a in arrays.values()) / 1024:.1f} KiB)')
+    parts, size = [{}], 0
+    for k, a in arrays.items():
+        cost = a.nbytes + 512   # (+ the entry's npy and zip headers)
+        if parts[-1] and size + cost > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += cost
+    for old in [HERE / f'{name}.npz', *HERE.glob(f'{name}.part*.npz')]:
+        old.unlink(missing_ok=True)
+    files = [f'{name}.npz'] if len(parts) == 1 else [f'{name}.part{i + 1}.npz' for i in range(len(parts))]
+    for f, part in zip(files, parts):
+        np.savez(HERE / f, **part)
+    print(f'wrote {", ".join(files)}  ({sum(a.nbytes for a in arrays.values()) / 1024:.1f} KiB)')
 
 
 def sd_arrays(prefix, sd):

@@ -6,7 +6,8 @@ fractal_experiments/frala_easy_final/final_fractal_agent.pt (tests/golden/fracta
 made by tests/golden/make_fractal_layout.py).  The forward numerics of the reference's own fractal
 arithmetic (level embedding, post-norm block order, global-state update, level projections, final
 aggregation, heads) are pinned by tests/test_fractal_golden.py: oracle/fractal_ref.py reproduces the
-reference's fractal_rl.py run in the build container (tests/golden/fractal.npz) to fp32 rounding.
+reference's fractal_rl.py run (tests/golden/fractal.part*.npz) to fp32 rounding; the checkpoint's
+weights themselves are tests/golden/fractal_easy_weights.part*.npz (loaded strictly below).
 Only the x-transformers Attention / FeedForward internals inside those modules remain the
 restatement's (x-transformers is absent).  The GPU tests compare the HIP path with that oracle, in
 fp64, within 1e-4 of the output scale."""
@@ -21,7 +22,6 @@ from oracle import fractal_ref as FR
 
 REPO = Path(__file__).resolve().parent.parent
 GOLDEN = REPO / 'tests' / 'golden' / 'fractal_easy_layout.json'
-CKPT = Path('/root/reference/fractal_experiments/frala_easy_final/final_fractal_agent.pt')
 
 DEMO_ARCHS = [   # comprehensive_demo.py:26-58 and its printed parameter counts (:340, :347, :354)
     (dict(input_dim=8, embed_dim=128, num_levels=2, heads=4, share_weights=True), 610_176),
@@ -59,15 +59,16 @@ def test_checkpoint_layout_matches_reference():
     assert ours == g['layout']
 
 
-@pytest.mark.skipif(not CKPT.exists(), reason='reference checkpoint only in the build container')
-def test_checkpoint_loads_strict():
+def test_checkpoint_loads_strict(golden):
+    """The checkpoint's world-model weights (tests/golden/fractal_easy_weights, the tensors of its
+    ``world_model`` entry bit for bit) load strictly and keep the recorded per-tensor sums."""
     wm, g = _easy_model()
-    ck = torch.load(CKPT, weights_only=True, map_location='cpu')
-    wm.load_state_dict(ck['world_model'], strict=True)
+    world_model = {k: torch.from_numpy(v) for k, v in golden('fractal_easy_weights').items()}
+    wm.load_state_dict(world_model, strict=True)
     for k, v in wm.state_dict().items():
         assert abs(float(v.double().sum()) - g['sums'][k]) <= 1e-9 * max(1.0, abs(g['sums'][k])), k
     # the oracle runs on the trained weights
-    sd = {k: v.double() for k, v in ck['world_model'].items()}
+    sd = {k: v.double() for k, v in world_model.items()}
     x = torch.randn(2, 5, 8, dtype=torch.float64, generator=torch.Generator().manual_seed(0))
     raw, val, _, _, levels = FR.world_model_forward(sd, x, 2, 4, g['layout'][
         'fractal_encoder.fractal_block.self_attn.to_q.weight'][0] // 4, share_weights=True, pre=None)

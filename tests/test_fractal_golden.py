@@ -1,6 +1,6 @@
 """Pin oracle/fractal_ref.py against the reference's OWN fractal modules (CPU).
 
-tests/golden/fractal.npz comes from tests/golden/make_golden.py, which executes
+tests/golden/fractal.part*.npz come from tests/golden/make_golden.py, which executes
 x_transformers_rl/fractal_rl.py in the build container with x-transformers' Attention / FeedForward
 restated (oracle/thirdparty.py XAttention / FeedForward).  So these fixtures pin the reference's
 own arithmetic — level embedding (learned + sinusoidal scale, fractal_rl.py:50-67), the post-norm

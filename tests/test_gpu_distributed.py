@@ -416,7 +416,7 @@ def test_bench_self_launches_two_ranks(tmp_path):
     env = dict(os.environ, XTRL_BENCH_BACKEND='gloo')
     env.pop('WORLD_SIZE', None)
     p = subprocess.run([sys.executable, '-u', str(REPO / 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0',
-                        '--no-cpu-baseline', '--no-roofline'], cwd=str(REPO), env=env, capture_output=True, text=True,
+                        '--full', '--no-cpu-baseline', '--no-roofline'], cwd=str(REPO), env=env, capture_output=True, text=True,
                        timeout=540)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([x for x in p.stdout.splitlines() if x.startswith('{')][-1])
@@ -425,3 +425,45 @@ def test_bench_self_launches_two_ranks(tmp_path):
     assert line['dp']['world_size'] == 2
     assert line['dp']['grad_allreduces_per_step'] == 3
     assert line['ppo_loss'] is not None and line['ppo_loss']['rel_delta'] <= 1e-4, line['ppo_loss']
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_asked_for_and_dumps_outputs(tmp_path):
+    """``bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR`` (the small C1 config): the line
+    holds the headline fields and ``ms_per_step`` = the timed wall time over the 3 steps asked for,
+    nothing that takes runs of its own (no roofline pass, loss delta or CPU baseline: ``--full``), and
+    DIR holds the last update's outputs as float32 / float64 arrays within the byte budget."""
+    import json
+    import subprocess
+    import numpy as np
+    import bench
+    out = tmp_path / 'dump'
+    p = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--config', 'c1', '--dump-outputs', str(out)], cwd=str(REPO), capture_output=True, text=True,
+                       timeout=120)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [x for x in p.stdout.splitlines() if x.startswith('{')]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line['metric'] == 'env-steps/s (rollout+update)' and line['unit'] == 'env-steps/s'
+    assert line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert line['steps'] == 3 and line['warmup'] == 1 and 'timed: 3 updates' in p.stderr
+    assert line['ms_per_step'] > 0 and line['value'] > 0
+    # value = env-steps / elapsed and ms_per_step = elapsed / steps describe the same timed region
+    # (value is printed to 0.1 env-steps/s, ms_per_step to 0.01 ms)
+    elapsed = line['config']['env_steps'] / line['value']
+    assert abs(1e3 * elapsed / 3 - line['ms_per_step']) <= 0.01 + 1e-3 * line['ms_per_step']
+    for k in ('roofline', 'attention_roofline', 'value_probed', 'cpu_baseline', 'ppo_loss'):
+        assert line[k] is None, k
+    arrays = {f.stem: np.load(f, allow_pickle=False) for f in out.glob('*.npy')}
+    assert {'episodes', 'lens', 'cum_reward', 'traj_states', 'traj_actions', 'traj_logp', 'traj_rewards',
+            'traj_values', 'params', 'ema_params', 'rs_mean', 'rs_var'} <= set(arrays)
+    assert sum(a.nbytes for a in arrays.values()) <= bench.DUMP_BUDGET == 64 << 20
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), k
+    cfg = bench.CONFIGS['c1']
+    lens = arrays['lens']
+    assert lens.shape == (cfg['episodes'],) and lens.min() >= 1 and lens.max() <= cfg['T']
+    assert lens.sum() <= line['config']['env_steps']     # (the last of the three updates' env-steps)
+    assert arrays['traj_states'].shape == (len(arrays['episodes']), cfg['T'], cfg['S'])
+    assert np.abs(arrays['params']).max() > 0 and np.abs(arrays['traj_values']).max() > 0

@@ -302,3 +302,55 @@ def test_bench_refuses_gpus_world_size_mismatch():
     p = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '1'], env=env, capture_output=True,
                        text=True, timeout=120)
     assert p.returncode != 0 and 'WORLD_SIZE=2' in p.stderr
+
+
+def test_bench_dump_outputs_samples_within_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs on a stand-in for the last update's results: float32 / float64 .npy files
+    within the byte budget, the episode and parameter samples fixed by the seed (two dumps equal, the
+    sampled rows are the source rows), positions past an episode's end zeroed, every length kept."""
+    from types import SimpleNamespace
+    import bench
+    g = torch.Generator().manual_seed(0)
+    E, T, S, B, n = 40, 12, 3, 7, 5000
+    lens = torch.randint(1, T + 1, (E,), generator=g, dtype=torch.int32)
+    traj = dict(states=torch.randn(E, T, S, generator=g), actions=torch.randint(0, 4, (E, T), generator=g).int(),
+                actions_f=None, logp=torch.randn(E, T, generator=g), rewards=torch.randn(E, T, generator=g),
+                bounds=torch.zeros(E, T, dtype=torch.uint8), values=torch.randn(E, T, B, generator=g))
+    traj['values'][:, -1] = float('inf')   # stale data past the episodes' ends
+    traj['values'][torch.arange(E), (lens - 1).long()] = 1.   # (an episode of length T keeps its last step)
+    agent = SimpleNamespace(flat=SimpleNamespace(flat=torch.randn(n, generator=g)), ema_flat=torch.randn(n, generator=g),
+                            rs_mean=torch.randn(S + 1, generator=g), rs_var=torch.rand(S + 1, generator=g))
+    learner = SimpleNamespace(agent=agent)
+    monkeypatch.setattr(bench, 'LAST', dict(traj=traj, lens=lens, cum=torch.randn(E, generator=g).double()))
+    budget = 24000
+    monkeypatch.setattr(bench, 'DUMP_BUDGET', budget)
+    per_episode = (T * S + 4 * T + T * B) * 4
+    assert E * per_episode > budget // 3 and n * 8 > budget // 2   # both samples are exercised
+    a, b = tmp_path / 'a', tmp_path / 'b'
+    written = bench.dump_outputs(a, learner, seed=3)
+    assert bench.dump_outputs(b, learner, seed=3) == written
+    files = sorted(p.name for p in a.glob('*'))
+    assert files == sorted(f'{k}.npy' for k in (
+        'episodes', 'lens', 'cum_reward', 'traj_states', 'traj_actions', 'traj_logp', 'traj_rewards', 'traj_bounds',
+        'traj_values', 'param_index', 'params', 'ema_params', 'rs_mean', 'rs_var'))
+    out = {p.stem: np.load(p, allow_pickle=False) for p in a.glob('*.npy')}
+    assert sum(v.nbytes for v in out.values()) == written <= budget
+    for k, v in out.items():
+        assert v.dtype in (np.float32, np.float64), k
+        assert np.isfinite(v).all(), k
+        np.testing.assert_array_equal(v, np.load(b / f'{k}.npy'), err_msg=k)
+    ep = out['episodes'].astype(np.int64)
+    assert len(ep) == (budget // 3) // per_episode and (np.diff(ep) > 0).all() and ep.min() >= 0 and ep.max() < E
+    np.testing.assert_array_equal(out['lens'], lens.numpy())
+    for k in ('states', 'actions', 'logp', 'rewards', 'bounds', 'values'):
+        want = traj[k][ep].float().numpy().copy()
+        for i, e in enumerate(ep):
+            want[i, int(lens[e]):] = 0
+        np.testing.assert_array_equal(out[f'traj_{k}'], want, err_msg=k)
+    idx = out['param_index'].astype(np.int64)
+    assert len(idx) == (budget // 2) // 16 and (np.diff(idx) > 0).all()
+    np.testing.assert_array_equal(out['params'], agent.flat.flat.numpy()[idx])
+    np.testing.assert_array_equal(out['ema_params'], agent.ema_flat.numpy()[idx])
+    # another seed draws another sample
+    bench.dump_outputs(tmp_path / 'c', learner, seed=4)
+    assert not np.array_equal(np.load(tmp_path / 'c' / 'episodes.npy'), out['episodes'])
