@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 21
+#define XTRL_ABI_VERSION 22
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -233,6 +233,10 @@ typedef struct XtrlDecodeDesc {
    * there (and the rollout start its -1 / 0 reset), so xtrl_host_decode passed this same buffer only
    * synchronises — no device->host copy per step */
   void* act_host;
+  /* world_model['attn_max_attend_past'] (x-transformers Attention max_attend_past; ABI 22): the step-t
+   * query attends the cached keys j with t - j <= attn_window only (at most attn_window + 1 keys; the
+   * cache keeps its [E][H][Tmax][dh] layout, the saving is in reads).  0: no window */
+  int attn_window;
 } XtrlDecodeDesc;
 
 /* Reset: state_0 = sim reset, prev_action = -1 / 0, prev_reward = 0, alive = 1, lens = 0, and
@@ -419,6 +423,22 @@ int xtrl_attn_bwd_part(const float* q, const float* k, const float* v, const int
                        const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
                        float* dq_part, int64_t dq_part_floats, int b, int H, int n, int dh, float scale,
                        float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, void* stream);
+/* The three entry points above with a sliding window (x-transformers Attention max_attend_past; ABI 22):
+ * key j is visible to query i iff j <= i, i - j <= window and j < lens[b] — at most window + 1 keys a
+ * row; the 64-key tiles wholly outside the band are skipped.  The dropout keep bits stay keyed by the
+ * absolute (i, j): a window draws the same bits as no window.  window = 0: no window (the entry points
+ * above are these with window = 0); window < 0 is an argument error. */
+int xtrl_attn_fwd_win(const float* q, const float* k, const float* v, const int32_t* lens, float* o, float* lse,
+                      int b, int H, int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset,
+                      uint32_t sub, int window, void* stream);
+int xtrl_attn_bwd_win(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                      const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws, int b,
+                      int H, int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset,
+                      uint32_t sub, int window, void* stream);
+int xtrl_attn_bwd_part_win(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                           const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                           float* dq_part, int64_t dq_part_floats, int b, int H, int n, int dh, float scale,
+                           float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, int window, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Learn-step forward / backward of WorldModelActorCritic on one minibatch, hand-scheduled (no
@@ -592,6 +612,9 @@ typedef struct XtrlTrainDesc {
   int32_t* ep_off;
   float* pack_ws;
   int64_t pack_ws_floats;
+  /* world_model['attn_max_attend_past'] (ABI 22): query i attends key j iff j <= i, i - j <= attn_window
+   * and j < lens (xtrl_attn_fwd_win / xtrl_attn_bwd_part_win); 0: no window */
+  int attn_window;
 } XtrlTrainDesc;
 
 int xtrl_train_forward(const XtrlTrainDesc* desc, void* stream);

@@ -9,7 +9,9 @@ every (t, R) point makes the first R slots live (alive = 1, the rest dead) and r
 decode step at position t ``warm + reps`` times; HIP events around every attention launch of the
 timed reps (XtrlDecodeDesc.prof_events) give the event time.  Algorithmic bytes per launch as
 bench.py's DecodeAttnTimer: per live (row, head) the K and V rows 0..t-1 (2 t dh fp32) + the row's
-q|k|v|gate|mix operands + the value-residual row + the K/V append + the output.
+q|k|v|gate|mix operands + the value-residual row + the K/V append + the output.  ``run --window W`` sets
+XtrlDecodeDesc.attn_window (world_model['attn_max_attend_past']): the step reads the last min(t, W)
+cached keys only, and the bytes count those.
 ``summarize`` assigns the k_attn_decode dispatches of a rocprofv3 --kernel-trace (and optional
 --pmc FETCH_SIZE / WRITE_SIZE) run of ``run`` to the points in launch order (the points are run
 in a fixed order, (warm + reps) x L dispatches each) and reports the profiler's duration and the
@@ -37,8 +39,10 @@ def points():
     return [(t, r) for r in RS for t in TS]
 
 
-def algo_bytes(c, t, R):
+def algo_bytes(c, t, R, window=0):
     H, dh = c.heads, c.dim_head
+    if window:
+        t = min(t, window)   # cached keys max(0, t - W) .. t - 1
     row = 3 * dh + (dh if c.gate_values else 0) + (1 if c.learned_mix else 0)
     vres = dh if c.value_residual else 0
     return 4.0 * R * H * (2 * t * dh + row + vres + 2 * dh + dh)
@@ -55,6 +59,7 @@ def run(a):
     eng = learner._engine_for(env, 512)
     c = eng.c
     L = c.depth
+    eng.desc.attn_window = a.window
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * 512 * L)]
     for e in ev:
         e.record()
@@ -74,11 +79,11 @@ def run(a):
                 ms += sum(ev[2 * (t * L + l)].elapsed_time(ev[2 * (t * L + l) + 1]) for l in range(L))
         eng.desc.prof_events = None
         us = ms * 1e3 / (a.reps * L)
-        b = algo_bytes(c, t, R)
-        out.append(dict(t=t, rows=R, us_event=round(us, 2), bytes=b, gbs_event=round(b / us / 1e3, 1),
+        b = algo_bytes(c, t, R, a.window)
+        out.append(dict(t=t, rows=R, window=a.window, us_event=round(us, 2), bytes=b, gbs_event=round(b / us / 1e3, 1),
                         frac_event=round(b / us / 1e3 / HBM, 4)))
         print(json.dumps(out[-1]), flush=True)
-    json.dump(dict(points=out, reps=a.reps, warm=WARM, layers=L), open(a.out, 'w'), indent=1)
+    json.dump(dict(points=out, reps=a.reps, warm=WARM, layers=L, window=a.window), open(a.out, 'w'), indent=1)
 
 
 def summarize(a):
@@ -127,6 +132,7 @@ if __name__ == '__main__':
     sub = ap.add_subparsers(dest='cmd', required=True)
     r = sub.add_parser('run')
     r.add_argument('--reps', type=int, default=10)
+    r.add_argument('--window', type=int, default=0, help='sliding window (attn_max_attend_past); 0: none')
     r.add_argument('--out', default=str(REPO / 'gpurun_out' / 'attn_sweep.json'))
     s = sub.add_parser('summarize')
     s.add_argument('json')

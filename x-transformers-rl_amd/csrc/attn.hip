@@ -56,7 +56,9 @@ struct AttnArgs {
   uint32_t offset;
   uint32_t c3;        // rng_c3(FIELD_DROPOUT, layer); byte mode: rng_c3(FIELD_DROPOUT, layer | 1 << 23)
   int causal;
+  int window;         // sliding window W: key j visible to query i only if i - j <= W (NO_WINDOW: none)
 };
+constexpr int NO_WINDOW = 1 << 30;   // (i - j <= NO_WINDOW always holds; band tile ranges become the causal ones)
 
 // first row of episode b in layout L: b * sb (padded [b][n] tokens), or ep_off[b] rows (packed)
 __device__ __forceinline__ int64_t ebase(const AttnArgs& a, const AttnLayout& L, int b) {
@@ -98,7 +100,10 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
   for (int d = 0; d < ND; ++d) o[d] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
   const int last_key = min(min(a.causal ? q0 + TQ - 1 : n - 1, n - 1), len - 1);
-  for (int kt = 0; kt * TK <= last_key; ++kt) {
+  // the first key tile of the band: row q0's oldest visible key q0 - W.  A later row of the tile may
+  // see nothing in it (its band starts in the next tile): it carries m = -inf, l = 0, o = 0 on
+  // (alpha and p below are 0 then: no exp(-inf + inf))
+  for (int kt = max(0, q0 - a.window) / TK; kt * TK <= last_key; ++kt) {
     __syncthreads();
     for (int x = tid; x < TK * DH; x += 256) {
       const int j = x / DH, c = x - j * DH, jj = kt * TK + j;
@@ -132,7 +137,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
 #pragma unroll
       for (int sub = 0; sub < 4; ++sub) {
         const int j = kt * TK + 16 * sub + lr;
-        const bool ok = (j <= i || !a.causal) && (j < len);
+        const bool ok = (j <= i || !a.causal) && (j < len) && (i - j <= a.window);
         sv[sub] = ok ? sacc[sub][r] * a.scale : -INFINITY;
         mx = fmaxf(mx, sv[sub]);
       }
@@ -168,15 +173,19 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
   for (int r = 0; r < 4; ++r) {
     const int i = q0 + 16 * w + 4 * lg + r;
     if (i < n) {
+      // a padded row (i >= len) whose whole band lies past the valid keys saw nothing: o = 0, lse = 0
+      // here; k_attn_dead_fwd then stores its uniform average (no window: every row of an episode
+      // with a valid key sees key 0)
+      const bool dead = a.window != NO_WINDOW && l[r] == 0.f;
 #pragma unroll
       for (int d = 0; d < ND; ++d) {
         const int64_t at = ob + (int64_t)i * osi + 16 * d + lr;
-        const float ov = o[d][r] / l[r];
+        const float ov = dead ? 0.f : o[d][r] / l[r];
         a.Oout[at] = ov;
         if (a.OGout)   // gated values (x-transformers attn_gate_values)
           a.OGout[at] = ov * sigmoidf_(a.G[ebase(a, a.gate, b) + h * a.gate.sh + (int64_t)i * a.gate.si + 16 * d + lr]);
       }
-      if (lr == 0) a.LSEout[(int64_t)bh * ns + i] = m[r] + logf(l[r]);
+      if (lr == 0) a.LSEout[(int64_t)bh * ns + i] = dead ? 0.f : m[r] + logf(l[r]);
     }
   }
 }
@@ -189,8 +198,14 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
 // <= 64 steps: min(qt, (len - 1) / 64) = 0) gets dQ written here, bit-identical to k_attn_bwd_dq;
 // the other rows get one partial per contributing key tile in dQp, summed in ascending key-tile
 // order by k_attn_dq_reduce.  (141 registers, 3 waves per SIMD: held to 128 it spilled 12.)
-template <int DH, bool DQ = false>
-__global__ __launch_bounds__(256, DH == 16 ? (DQ ? 3 : 4) : 1) void k_attn_bwd_dkdv(const AttnArgs a) {
+// With a window W the contributing key tiles of query tile qt are max(0, 64 qt - W) / 64 ..
+// min(qt, (len - 1) / 64): one tile -> dQ directly, several -> partials, none (padded rows past the
+// band) -> the reduce stores 0.
+// WIN = false (dh = 16 without a window, the C2 / C3 shapes): the window tests are compiled out — with
+// them the 128-register budget of the 4-waves-per-SIMD form spilled 2 registers; every other form
+// takes the window at run time (NO_WINDOW: none)
+template <int DH, bool DQ = false, bool WIN = true>
+__global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_attn_bwd_dkdv(const AttnArgs a) {
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Qs[TQ][KST], dOs[TQ][KST];
   __shared__ float Ks[DQ ? TK : 1][KST];
@@ -238,8 +253,16 @@ __global__ __launch_bounds__(256, DH == 16 ? (DQ ? 3 : 4) : 1) void k_attn_bwd_d
       }
     }
   }
-  if (j0 < len) {
-    for (int qt = j0 / TQ; qt * TQ < n; ++qt) {
+  // a key tile without a valid key (a tile of padded rows) under WIN: its workgroup still owns the D
+  // of its own query tile — it stages that one tile, stores D (the very same sum) and stops there
+  // (without a window the key-tile-0 workgroup visits every query tile and stays the owner, as it
+  // always was: no extra staging)
+  const bool live = j0 < len;
+  const bool own0 = !WIN || a.window == NO_WINDOW;
+  if (live || (!own0 && len > 0)) {
+    // query tiles of the band: from the diagonal to the last one holding a row <= j0 + TK - 1 + W
+    const int n_end = !WIN ? n : (live ? min(n, j0 + TK + a.window) : min(n, j0 + TQ));
+    for (int qt = j0 / TQ; qt * TQ < n_end; ++qt) {
       __syncthreads();
       for (int x = tid; x < TQ * DH; x += 256) {
         const int i = x / DH, c = x - i * DH, ii = qt * TQ + i;
@@ -248,7 +271,8 @@ __global__ __launch_bounds__(256, DH == 16 ? (DQ ? 3 : 4) : 1) void k_attn_bwd_d
       }
       // D_i = rowsum(dO_i * O_i) of the tile's query rows, computed here (the O row in registers
       // while the tile stages) in the order of a sequential sum over the head dimension; the
-      // key-tile-0 workgroup, which visits every query tile, stores it for k_attn_bwd_dq
+      // diagonal workgroup (key tile == query tile: a row always sees itself, so a window never
+      // skips the pair) stores it for k_attn_bwd_dq
       float orow[DH];
       if (tid < TQ) {
         const int ii = qt * TQ + tid;
@@ -263,8 +287,9 @@ __global__ __launch_bounds__(256, DH == 16 ? (DQ ? 3 : 4) : 1) void k_attn_bwd_d
 #pragma unroll
         for (int c = 0; c < DH; ++c) dsum += dOs[tid][c] * orow[c];
         Dls[tid] = dsum;
-        if (j0 == 0 && ii < n) a.Dout[(int64_t)bh * ns + ii] = dsum;
+        if ((own0 ? j0 == 0 : qt * TQ == j0) && ii < n) a.Dout[(int64_t)bh * ns + ii] = dsum;
       }
+      if (WIN && !live) break;   // (workgroup-uniform)
       __syncthreads();
       float dsr[4][4];
 #pragma unroll
@@ -301,7 +326,8 @@ __global__ __launch_bounds__(256, DH == 16 ? (DQ ? 3 : 4) : 1) void k_attn_bwd_d
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int j = j0 + 16 * w + 4 * lg + r;
-          const bool ok = (j <= i) && (j < len) && (i < n);
+          // 0 <= i - j <= W in one compare
+          const bool ok = (WIN ? (unsigned)(i - j) <= (unsigned)a.window : j <= i) && (j < len) && (i < n);
           const float p = ok ? expf(st[r] * a.scale - Ls[il]) : 0.f;
           float z = 1.f;
           if (a.thresh8 && ok) z = (kq[r] >= a.thresh8) ? a.inv_keep : 0.f;
@@ -338,7 +364,8 @@ __global__ __launch_bounds__(256, DH == 16 ? (DQ ? 3 : 4) : 1) void k_attn_bwd_d
             dq[d] = mfma16(Ps[j >> 4][j & 15][16 * w + lr], Ks[j][16 * d + lr], dq[d]);
           }
         }
-        const bool sole = min(qt, kmax) == 0;   // (then this is key tile 0)
+        // the key tiles visiting this query tile: max(0, qt TQ - W) / TK .. min(qt, kmax); one: dQ directly
+        const bool sole = (WIN ? max(0, qt * TQ - a.window) / TK : 0) == min(qt, kmax);
         const int64_t pb = ((int64_t)blockIdx.x * gridDim.y + bh) * ns;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -370,8 +397,8 @@ __global__ __launch_bounds__(256, DH == 16 ? (DQ ? 3 : 4) : 1) void k_attn_bwd_d
 }
 
 // dQ of the rows with more than one contributing key tile: the partials of key tiles
-// 0 .. min(qt, (len - 1) / 64) summed in ascending order (k_attn_bwd_dkdv<DH, true>); thread per
-// (row, 4 channels)
+// max(0, qt 64 - W) / 64 .. min(qt, (len - 1) / 64) — exactly the tiles that wrote one — summed in
+// ascending order (k_attn_bwd_dkdv<DH, true>); thread per (row, 4 channels)
 template <int DH>
 __global__ __launch_bounds__(256) void k_attn_dq_reduce(const AttnArgs a, int BH) {
   constexpr int C4 = DH / 4;
@@ -384,10 +411,13 @@ __global__ __launch_bounds__(256) void k_attn_dq_reduce(const AttnArgs a, int BH
   const int b = bh / a.H, h = bh - b * a.H;
   const int len = a.lens[b];
   if (a.ep_off && i >= min(len, ns)) return;   // packed rows: past the episode's own length
-  const int m = min(i / TQ, len > 0 ? (len - 1) / TK : 0);
-  if (m == 0) return;   // written by key tile 0
-  float4 acc = *reinterpret_cast<const float4*>(a.dQp + ((int64_t)bh * ns + i) * DH + 4 * c4);
-  for (int kt = 1; kt <= m; ++kt) {
+  if (len <= 0) return;   // zero-filled by the key-tile-0 workgroup
+  const int qt = i / TQ;
+  const int m = min(qt, (len - 1) / TK), f = max(0, qt * TQ - a.window) / TK;
+  if (m == f) return;   // one key tile visits the row's query tile: written by it
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);   // f > m: none does (padded rows past the band): dQ = 0
+  if (f < m) acc = *reinterpret_cast<const float4*>(a.dQp + (((int64_t)f * BH + bh) * ns + i) * DH + 4 * c4);
+  for (int kt = f + 1; kt <= m; ++kt) {
     const float4 p = *reinterpret_cast<const float4*>(a.dQp + (((int64_t)kt * BH + bh) * ns + i) * DH + 4 * c4);
     acc.x += p.x;
     acc.y += p.y;
@@ -439,7 +469,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
 #pragma unroll
   for (int d = 0; d < ND; ++d) dq[d] = f32x4v{0.f, 0.f, 0.f, 0.f};
   const int last_key = min(min(a.causal ? q0 + TQ - 1 : n - 1, n - 1), len - 1);
-  for (int kt = 0; kt * TK <= last_key; ++kt) {
+  for (int kt = max(0, q0 - a.window) / TK; kt * TK <= last_key; ++kt) {   // the band's key tiles
     __syncthreads();
     for (int x = tid; x < TK * DH; x += 256) {
       const int j = x / DH, c = x - j * DH, jj = kt * TK + j;
@@ -467,7 +497,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = q0 + 16 * w + 4 * lg + r;
-        const bool ok = (j <= i) && (j < len) && (i < n);
+        const bool ok = ((unsigned)(i - j) <= (unsigned)a.window) && (j < len) && (i < n);   // 0 <= i - j <= W
         const float p = ok ? expf(s_[r] * a.scale - lse[r]) : 0.f;
         float z = 1.f;
         if (a.thresh8 && ok) z = (qbyte(kb8, sub, r) >= a.thresh8) ? a.inv_keep : 0.f;
@@ -542,10 +572,14 @@ __global__ __launch_bounds__(256) void k_attn_bwd_fused(const AttnArgs a) {
       dk[d] = f32x4v{0.f, 0.f, 0.f, 0.f};
       dv[d] = f32x4v{0.f, 0.f, 0.f, 0.f};
     }
-    if (j0 < len) {
+    const bool live = j0 < len;   // (else, with a window and a valid key in the episode: only D of the diagonal tile, as k_attn_bwd_dkdv)
+    const bool own0 = a.window == NO_WINDOW;   // no window: key tile 0 visits every query tile and owns D
+    if (live || (!own0 && len > 0)) {
 #pragma unroll
       for (int qt = 0; qt < FB_QT; ++qt) {
         if (qt < kt || qt >= nq) continue;   // (workgroup-uniform) causal: query tiles from the key tile on
+        if (!live && qt != kt) continue;
+        if (qt * TQ - (j0 + TK - 1) > a.window) continue;   // (workgroup-uniform) the pair lies outside the band
         __syncthreads();
         for (int x = tid; x < TQ * DH; x += 256) {
           const int i = x / DH, c = x - i * DH, ii = qt * TQ + i, jj = j0 + i;
@@ -567,8 +601,9 @@ __global__ __launch_bounds__(256) void k_attn_bwd_fused(const AttnArgs a) {
           for (int c = 0; c < DH; ++c) dsum += dOs[tid][c] * orow[c];
           Dls[tid] = dsum;
           const int ii = qt * TQ + tid;
-          if (kt == 0 && ii < n) a.Dout[(int64_t)bh * ns + ii] = dsum;   // as k_attn_bwd_dkdv's key tile 0
+          if ((own0 ? kt == 0 : kt == qt) && ii < n) a.Dout[(int64_t)bh * ns + ii] = dsum;   // as k_attn_bwd_dkdv
         }
+        if (!live) continue;   // (workgroup-uniform)
         __syncthreads();
         float dsr[4][4];
 #pragma unroll
@@ -600,7 +635,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_fused(const AttnArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int j = j0 + 16 * w + 4 * lg + r;
-            const bool ok = (j <= i) && (j < len) && (i < n);
+            const bool ok = ((unsigned)(i - j) <= (unsigned)a.window) && (j < len) && (i < n);   // 0 <= i - j <= W
             const float p = ok ? expf(st[r] * a.scale - Ls[il]) : 0.f;
             float z = 1.f;
             if (a.thresh8 && ok) z = (kq[r] >= a.thresh8) ? a.inv_keep : 0.f;
@@ -659,6 +694,72 @@ __global__ __launch_bounds__(256) void k_attn_bwd_fused(const AttnArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Rows that see no key under a window: the padded rows i >= len + W of the padded layout.
+// x-transformers fills masked scores with the finite -max, so such a row's softmax is uniform over
+// all n key positions (future and padded ones included), p_ij = 1 / n, and no gradient reaches its
+// scores.  They are padded tokens, but the scalar HL-Gauss mean puts them into the critic loss, so
+// they are reproduced.  The flash kernels leave these rows at o = 0 (dQ, dK contributions 0); these
+// two launches add the uniform part:
+//   forward   o_i = sum_j z_ij v_j / n (and its gated copy)
+//   backward  dv_j += sum_{dead i} z_ij do_i / n
+// z_ij: the dropout keep factor of the same absolute (i, j) stream.  Thread per (row, channel); a row's
+// DH lanes run together (they leave together: the exits below depend on the row only).
+__device__ __forceinline__ float keep_scale(const AttnArgs& a, uint32_t off, int i, int j) {
+  if (a.thresh8) {
+    const u32x4_t r = philox4x32_10((uint32_t)(i >> 2), (uint32_t)(16 * (j >> 6) + (j & 15)), off, a.c3, a.seed);
+    return qbyte(r, (j >> 4) & 3, i & 3) >= a.thresh8 ? a.inv_keep : 0.f;
+  }
+  if (a.thresh) return keep_word(a.seed, off, a.c3, i, j) >= a.thresh ? a.inv_keep : 0.f;
+  return 1.f;
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void k_attn_dead_fwd(const AttnArgs a) {
+  const int c = threadIdx.x % DH, i = blockIdx.x * (256 / DH) + threadIdx.x / DH;
+  const int bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H, n = a.n;
+  const int len = a.lens[b];
+  if (len <= 0 || i >= n || i < len + a.window) return;
+  const int64_t ib = ebase(a, a.in, b) + h * a.in.sh, ob = ebase(a, a.out, b) + h * a.out.sh;
+  const uint32_t off = a.offset + (uint32_t)bh;
+  // (the DH lanes of a row each draw the keep factor of one key and hand it round: one Philox
+  // block per (row, key), not per channel)
+  float acc = 0.f;
+  for (int j0 = 0; j0 < n; j0 += DH) {
+    const float zm = j0 + c < n ? keep_scale(a, off, i, j0 + c) : 0.f;
+    for (int jj = 0; jj < DH; ++jj) {
+      const float z = __shfl(zm, jj, DH);
+      if (j0 + jj < n) acc += z * a.V[ib + (int64_t)(j0 + jj) * a.in.si + c];
+    }
+  }
+  const float ov = acc / (float)n;
+  const int64_t at = ob + (int64_t)i * a.out.si + c;
+  a.Oout[at] = ov;
+  if (a.OGout) a.OGout[at] = ov * sigmoidf_(a.G[ebase(a, a.gate, b) + h * a.gate.sh + (int64_t)i * a.gate.si + c]);
+}
+
+template <int DH>
+__global__ __launch_bounds__(256) void k_attn_dead_bwd(const AttnArgs a) {
+  const int c = threadIdx.x % DH, j = blockIdx.x * (256 / DH) + threadIdx.x / DH;
+  const int bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H, n = a.n;
+  const int len = a.lens[b];
+  if (len <= 0 || j >= n) return;
+  const int64_t ob = ebase(a, a.out, b) + h * a.out.sh, gb = ebase(a, a.grad, b) + h * a.grad.sh;
+  const uint32_t off = a.offset + (uint32_t)bh;
+  float acc = 0.f;
+  for (int i0 = len + a.window; i0 < n; i0 += DH) {
+    const float zm = i0 + c < n ? keep_scale(a, off, i0 + c, j) : 0.f;
+    for (int ii = 0; ii < DH; ++ii) {
+      const float z = __shfl(zm, ii, DH);
+      if (i0 + ii < n) acc += z * a.dO[ob + (int64_t)(i0 + ii) * a.out.si + c];
+    }
+  }
+  if (len + a.window < n) a.dV[gb + (int64_t)j * a.grad.si + c] += acc / (float)n;
+}
+
+// whether a problem can have such rows: a window, the padded layout, and a row n - 1 >= 1 + W
+bool has_dead_rows(const AttnProblem& p) { return p.window > 0 && !p.ep_off && p.window <= p.n - 2; }
+
 bool attn_fused_bwd_on() {   // XTRL_ATTN_FUSED_BWD=0: the kernel pair (read per launch: tests flip it)
   const char* e = getenv("XTRL_ATTN_FUSED_BWD");
   return !(e && atoi(e) == 0);
@@ -685,6 +786,9 @@ int fill_args(AttnArgs& a, const AttnProblem& p) {
   a.c3 = rng_c3(FIELD_DROPOUT, a.thresh8 ? (p.sub | (1u << 23)) : p.sub);
   a.causal = p.causal;
   a.ep_off = p.ep_off;
+  XTRL_REQUIRE(p.window >= 0, "attn: window %d < 0 (0 = no window)", p.window);
+  XTRL_REQUIRE(p.window == 0 || p.causal, "attn: a window needs causal attention");
+  a.window = p.window > 0 ? min(p.window, NO_WINDOW) : NO_WINDOW;
   return XTRL_OK;
 }
 
@@ -708,6 +812,13 @@ int attn_fwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   else if (p.dh == 32) hipLaunchKernelGGL(k_attn_fwd<32>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_attn_fwd<64>, grid, dim3(256), 0, s, a);
   XTRL_LAUNCHED("attn_fwd");
+  if (has_dead_rows(p)) {
+    dim3 dgrid((p.n + 256 / p.dh - 1) / (256 / p.dh), p.b * p.H);
+    if (p.dh == 16) hipLaunchKernelGGL(k_attn_dead_fwd<16>, dgrid, dim3(256), 0, s, a);
+    else if (p.dh == 32) hipLaunchKernelGGL(k_attn_dead_fwd<32>, dgrid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_attn_dead_fwd<64>, dgrid, dim3(256), 0, s, a);
+    XTRL_LAUNCHED("attn_dead_fwd");
+  }
   return XTRL_OK;
 }
 
@@ -729,7 +840,7 @@ int attn_bwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   a.dQ = dq;
   a.dK = dk;
   a.dV = dv;
-  // (D = rowsum(dO * O) is formed inside k_attn_bwd_dkdv, whose key-tile-0 workgroups store it for dq)
+  // (D = rowsum(dO * O) is formed inside k_attn_bwd_dkdv, whose diagonal workgroups store it for dq)
   dim3 grid((p.n + TQ - 1) / TQ, p.b * p.H);
   const int64_t part_need = attn_dq_part_floats(p.b, p.H, p.n, p.dh);
   if (p.dh == 16 && p.n <= FB_MAXN && attn_fused_bwd_on()) {   // short episodes: one fused launch
@@ -737,11 +848,13 @@ int attn_bwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   } else if (p.dh == 16 && p.dq_part && p.dq_part_floats >= part_need && attn_fused_bwd_on()) {
     // long episodes: dK / dV with the dQ pass folded in (partials for multi-key-tile rows) + their sum
     a.dQp = p.dq_part;
-    hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true>), grid, dim3(256), 0, s, a);
+    if (p.window > 0) hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, false>), grid, dim3(256), 0, s, a);
     const int64_t units = (int64_t)p.b * p.H * p.n * 4;
     hipLaunchKernelGGL(k_attn_dq_reduce<16>, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, a, p.b * p.H);
   } else if (p.dh == 16) {
-    hipLaunchKernelGGL(k_attn_bwd_dkdv<16>, grid, dim3(256), 0, s, a);
+    if (p.window > 0) hipLaunchKernelGGL(k_attn_bwd_dkdv<16>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_bwd_dkdv<16, false, false>), grid, dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_attn_bwd_dq<16>, grid, dim3(256), 0, s, a);
   } else if (p.dh == 32) {
     hipLaunchKernelGGL(k_attn_bwd_dkdv<32>, grid, dim3(256), 0, s, a);
@@ -751,6 +864,13 @@ int attn_bwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
     hipLaunchKernelGGL(k_attn_bwd_dq<64>, grid, dim3(256), 0, s, a);
   }
   XTRL_LAUNCHED("attn_bwd");
+  if (has_dead_rows(p)) {
+    dim3 dgrid((p.n + 256 / p.dh - 1) / (256 / p.dh), p.b * p.H);
+    if (p.dh == 16) hipLaunchKernelGGL(k_attn_dead_bwd<16>, dgrid, dim3(256), 0, s, a);
+    else if (p.dh == 32) hipLaunchKernelGGL(k_attn_dead_bwd<32>, dgrid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_attn_dead_bwd<64>, dgrid, dim3(256), 0, s, a);
+    XTRL_LAUNCHED("attn_dead_bwd");
+  }
   return XTRL_OK;
 }
 
@@ -759,42 +879,66 @@ int64_t attn_dq_part_floats(int b, int H, int n, int dh) {
 }
 
 AttnProblem contiguous_problem(const int32_t* lens, int b, int H, int n, int dh, float scale, float p, uint64_t seed,
-                               uint32_t offset, uint32_t sub) {
+                               uint32_t offset, uint32_t sub, int window) {
   AttnProblem pr{b, H, n, dh, lens, scale, p, seed, offset, {}, {}, {}, {}};
   pr.sub = sub;
+  pr.window = window;
   pr.in = pr.out = pr.grad = attn_layout_bhnd(H, n, dh);
   return pr;
 }
 
 }  // namespace xtrl
 
+extern "C" int xtrl_attn_fwd_win(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
+                                 float* lse, int b, int H, int n, int dh, float scale, float dropout_p, uint64_t seed,
+                                 uint32_t offset, uint32_t sub, int window, void* stream) {
+  return xtrl::attn_fwd_ex(xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window), q, k,
+                           v, o, lse, nullptr, nullptr, xtrl::as_stream(stream));
+}
+
 extern "C" int xtrl_attn_fwd(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
                              float* lse, int b, int H, int n, int dh, float scale, float dropout_p, uint64_t seed,
                              uint32_t offset, uint32_t sub, void* stream) {
-  return xtrl::attn_fwd_ex(xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub), q, k, v, o,
-                           lse, nullptr, nullptr, xtrl::as_stream(stream));
+  return xtrl_attn_fwd_win(q, k, v, lens, o, lse, b, H, n, dh, scale, dropout_p, seed, offset, sub, 0, stream);
 }
 
 extern "C" int64_t xtrl_attn_bwd_part_floats(int b, int H, int n, int dh) {
   return xtrl::attn_dq_part_floats(b, H, n, dh);
 }
 
+extern "C" int xtrl_attn_bwd_part_win(const float* q, const float* k, const float* v, const int32_t* lens,
+                                      const float* o, const float* lse, const float* dout, float* dq, float* dk,
+                                      float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats, int b, int H,
+                                      int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset,
+                                      uint32_t sub, int window, void* stream) {
+  xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window);
+  pr.dq_part = dq_part;
+  pr.dq_part_floats = dq_part_floats;
+  return xtrl::attn_bwd_ex(pr, q, k, v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+}
+
 extern "C" int xtrl_attn_bwd_part(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
                                   const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
                                   float* dq_part, int64_t dq_part_floats, int b, int H, int n, int dh, float scale,
                                   float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, void* stream) {
-  xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub);
-  pr.dq_part = dq_part;
-  pr.dq_part_floats = dq_part_floats;
-  return xtrl::attn_bwd_ex(pr, q, k, v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+  return xtrl_attn_bwd_part_win(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, dq_part, dq_part_floats, b, H, n, dh,
+                                scale, dropout_p, seed, offset, sub, 0, stream);
+}
+
+extern "C" int xtrl_attn_bwd_win(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                                 const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                                 int b, int H, int n, int dh, float scale, float dropout_p, uint64_t seed,
+                                 uint32_t offset, uint32_t sub, int window, void* stream) {
+  return xtrl::attn_bwd_ex(xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window), q, k,
+                           v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
 }
 
 extern "C" int xtrl_attn_bwd(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
                              const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
                              int b, int H, int n, int dh, float scale, float dropout_p, uint64_t seed,
                              uint32_t offset, uint32_t sub, void* stream) {
-  return xtrl::attn_bwd_ex(xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub), q, k, v, o,
-                           lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+  return xtrl_attn_bwd_win(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, b, H, n, dh, scale, dropout_p, seed,
+                           offset, sub, 0, stream);
 }
 
 /* bidirectional / causal attention forward on token-major operands (rows b * n + i, head h at

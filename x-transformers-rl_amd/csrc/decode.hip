@@ -397,11 +397,18 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
 #pragma unroll
     for (int i = 0; i < 4; ++i) gate4[i] = row[3 * I + h * DH + 4 * cq + i];
   }
-  // the first chunk of the cache (rows written by earlier steps; rows >= t clamped, masked below)
+  // the first chunk of the cache (rows written by earlier steps; rows >= t clamped, masked below).
+  // Sliding window (attn_window W > 0): the query at position t sees the keys j_lo = max(0, t - W) .. t
+  // only.  The cache pointers and the score slots are moved up by j_lo and the loops below run over
+  // the window-relative positions 0 .. tw = t - j_lo (loads clamped to [j_lo, t - 1] absolute) —
+  // W < 128: the windowed cache read is this one prefetch.  No window: j_lo = 0, tw = t
   const int64_t cache_base = ((int64_t)e * H + h) * D.Tmax * DH;
-  const float* Kc = Ly.k_cache + cache_base;
-  const float* Vc = Ly.v_cache + cache_base;
-  const int tl = max(t - 1, 0);
+  const int j_lo = D.attn_window > 0 ? max(t - D.attn_window, 0) : 0;
+  const int tw = t - j_lo;
+  const float* Kc = Ly.k_cache + cache_base + (int64_t)j_lo * DH;
+  const float* Vc = Ly.v_cache + cache_base + (int64_t)j_lo * DH;
+  sc += j_lo;
+  const int tl = max(tw - 1, 0);
   float4 kpre[KL][F4], vpre[VU];
 #pragma unroll
   for (int u = 0; u < KL; ++u)
@@ -435,7 +442,7 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
   for (int i = 0; i < DH; ++i) qreg[i] = qs[i];
   // scores, one key per lane; chunk 0 from the prefetched rows
   float mx = -INFINITY;
-  for (int j0 = 0; j0 <= t; j0 += CK) {
+  for (int j0 = 0; j0 <= tw; j0 += CK) {
     float4 kc[KL][F4];
     if (j0 == 0) {
 #pragma unroll
@@ -453,7 +460,7 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
     for (int u = 0; u < KL; ++u) {
       const int j = j0 + lane + 64 * u;
       float s = 0.f;
-      if (j < t) {
+      if (j < tw) {
 #pragma unroll
         for (int i = 0; i < F4; ++i) {
           s += qreg[4 * i] * kc[u][i].x;
@@ -466,7 +473,7 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
         for (int i = 0; i < DH; ++i) s += qreg[i] * ks[i];
       }
       s *= scale;
-      if (j <= t) {
+      if (j <= tw) {
         sc[j] = s;
         mx = fmaxf(mx, s);
       }
@@ -474,7 +481,7 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
   }
   mx = wave_max_dpp(mx);
   float sum = 0.f;
-  for (int j = lane; j <= t; j += 64) {
+  for (int j = lane; j <= tw; j += 64) {
     const float p = expf(sc[j] - mx);
     sc[j] = p;
     sum += p;
@@ -484,7 +491,7 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
   // P.V (unnormalised probabilities; one division at the end)
   const float4 vnew = make_float4(vs[4 * cq], vs[4 * cq + 1], vs[4 * cq + 2], vs[4 * cq + 3]);
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int j0 = 0; j0 <= t; j0 += CK) {
+  for (int j0 = 0; j0 <= tw; j0 += CK) {
     float4 vc[VU];
     if (j0 == 0) {
 #pragma unroll
@@ -497,9 +504,9 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
 #pragma unroll
     for (int u = 0; u < VU; ++u) {
       const int j = j0 + kk + KPI * u;
-      if (j <= t) {
+      if (j <= tw) {
         const float p = sc[j];
-        const float4 v4 = j < t ? vc[u] : vnew;
+        const float4 v4 = j < tw ? vc[u] : vnew;
         acc.x += p * v4.x;
         acc.y += p * v4.y;
         acc.z += p * v4.z;
@@ -959,6 +966,7 @@ int check_desc(const XtrlDecodeDesc* D) {
   XTRL_REQUIRE(D->n_qkv == 3 * I + (D->gate_values ? I : 0) + ((D->value_residual && D->learned_mix) ? D->H : 0),
                "decode: n_qkv mismatch");
   XTRL_REQUIRE(!D->ff_glu || (D->hglu && D->hff), "decode: ff_glu needs hglu");
+  XTRL_REQUIRE(D->attn_window >= 0, "decode: attn_window %d < 0 (0 = no window)", D->attn_window);
   return XTRL_OK;
 }
 
@@ -2047,14 +2055,22 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
         // scores of the cached keys, one key per lane, NP 64-key passes in flight
         constexpr int NP = KP;   // (DH 16: 128 keys per round trip; 256 measured slower: C2 rollout
                                  //  31.06-31.26 vs 30.80-30.92 ms, A/B x3)
+        // (sliding window: the cached keys j_lo = max(0, t - W) .. t - 1 — cache pointers and score slots
+        // moved up by j_lo, loops over the tw = t - j_lo window-relative positions, as k_attn_decode;
+        // no window: j_lo = 0, tw = t)
+        const int j_lo = D.attn_window > 0 ? max(t - D.attn_window, 0) : 0;
+        const int tw = t - j_lo;
+        const float* kcw = Ly.k_cache + cb + (int64_t)j_lo * DH;
+        const float* vcw = Ly.v_cache + cb + (int64_t)j_lo * DH;
+        float* scw = sc + j_lo;
         float mx = kn;
-        for (int j0 = 0; j0 < t; j0 += 64 * NP) {
+        for (int j0 = 0; j0 < tw; j0 += 64 * NP) {
           float4 kr[NP][F4];
 #pragma unroll
           for (int u = 0; u < NP; ++u) {
-            const int j = min(j0 + lane + 64 * u, t - 1);
+            const int j = min(j0 + lane + 64 * u, tw - 1);
 #pragma unroll
-            for (int i = 0; i < F4; ++i) kr[u][i] = reinterpret_cast<const float4*>(Ly.k_cache + cb + (int64_t)j * DH)[i];
+            for (int i = 0; i < F4; ++i) kr[u][i] = reinterpret_cast<const float4*>(kcw + (int64_t)j * DH)[i];
           }
 #pragma unroll
           for (int u = 0; u < NP; ++u) {
@@ -2069,17 +2085,17 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
               s_ += qv.w * kr[u][i].w;
             }
             s_ *= scale;
-            if (j < t) {
-              sc[j] = s_;
+            if (j < tw) {
+              scw[j] = s_;
               mx = fmaxf(mx, s_);
             }
           }
         }
         mx = wave_max_dpp(mx);
         float sum = 0.f;
-        for (int j = lane; j < t; j += 64) {
-          const float p = expf(sc[j] - mx);
-          sc[j] = p;
+        for (int j = lane; j < tw; j += 64) {
+          const float p = expf(scw[j] - mx);
+          scw[j] = p;
           sum += p;
         }
         const float pn = expf(kn - mx);
@@ -2089,17 +2105,17 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
         const int kk = lane % KPI, cq = lane / KPI;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         constexpr int VB = 8;   // value rows in flight per lane (128 / 64 / 32 keys a pass; 16 spilled)
-        for (int j0 = 0; j0 < t; j0 += VB * KPI) {
+        for (int j0 = 0; j0 < tw; j0 += VB * KPI) {
           float4 vr[VB];
 #pragma unroll
           for (int u = 0; u < VB; ++u) {
-            const int j = min(j0 + kk + KPI * u, t - 1);
-            vr[u] = *reinterpret_cast<const float4*>(Ly.v_cache + cb + (int64_t)j * DH + 4 * cq);
+            const int j = min(j0 + kk + KPI * u, tw - 1);
+            vr[u] = *reinterpret_cast<const float4*>(vcw + (int64_t)j * DH + 4 * cq);
           }
 #pragma unroll
           for (int u = 0; u < VB; ++u) {
             const int j = j0 + kk + KPI * u;
-            const float p = j < t ? sc[j] : 0.f;
+            const float p = j < tw ? scw[j] : 0.f;
             acc.x += p * vr[u].x;
             acc.y += p * vr[u].y;
             acc.z += p * vr[u].z;

@@ -210,6 +210,9 @@ struct AttnProblem {
   // packed rows (the learn step without padding, XtrlTrainDesc.packed): episode b's min(lens[b], n)
   // tokens are rows ep_off[b] .. of the token-major layouts (their sb unused); NULL: rows b * n + i
   const int32_t* ep_off = nullptr;
+  // sliding window (x-transformers max_attend_past): key j visible to query i only if i - j <= window,
+  // on top of the causal and key-padding masks; 0: no window
+  int window = 0;
 };
 int64_t attn_dq_part_floats(int b, int H, int n, int dh);
 

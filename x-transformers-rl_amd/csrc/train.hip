@@ -1147,6 +1147,7 @@ AttnProblem attn_problem(const Ctx& c, const XtrlTrainLayer& Ly, int li) {
   p.ep_off = D->packed ? D->ep_off : nullptr;
   p.dq_part = D->dq_part;
   p.dq_part_floats = D->dq_part_floats;
+  p.window = D->attn_window;
   return p;
 }
 

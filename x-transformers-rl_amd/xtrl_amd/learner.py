@@ -126,12 +126,17 @@ class Agent(nn.Module):
                 wm.pop(k)
         known = {'attn_dim_head', 'heads', 'depth', 'attn_gate_values', 'add_value_residual',
                  'learned_value_residual_mix', 'ff_mult', 'ff_no_bias', 'ff_glu', 'attn_qk_norm',
-                 'attn_qk_norm_scale', 'rotary_xpos', 'rotary_xpos_scale_base', 'use_rmsnorm'}
+                 'attn_qk_norm_scale', 'rotary_xpos', 'rotary_xpos_scale_base', 'use_rmsnorm',
+                 'attn_max_attend_past'}
         unknown = set(wm) - known
         if unknown:
             raise NotImplementedError(f'world_model options {sorted(unknown)} are not supported by the MI355X decoder '
                                       f'(supported: {sorted(known)}, implementation switches attn_flash / '
                                       f'attn_onnxable, and any option at its x-transformers default)')
+        # sliding window (x-transformers Attention max_attend_past): query i sees key j iff 0 <= i - j <= W
+        window = wm.get('attn_max_attend_past')
+        if window is not None and (isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1):
+            raise ValueError(f'attn_max_attend_past must be an int >= 1 or None (no window), not {window!r}')
         self.seed = int(seed)
         self.evolutionary = evolutionary
         self.evolve_every, self.evolve_after_step = evolve_every, evolve_after_step
@@ -149,7 +154,7 @@ class Agent(nn.Module):
                         qk_norm_scale=float(wm.get('attn_qk_norm_scale', 10.)),
                         rotary_xpos=bool(wm.get('rotary_xpos', False)),
                         xpos_scale_base=float(wm.get('rotary_xpos_scale_base', 512.)),
-                        rotary_abs_rollout=rotary_abs_rollout,
+                        rotary_abs_rollout=rotary_abs_rollout, attn_window=int(window or 0),
                         hl_reduction_mean=hl_reduction_mean, hl_sigma_ratio=hl_sigma_ratio)
         self.cfg = c
         # the learn step without the minibatch's padding (XtrlTrainDesc.packed): exact only with the
@@ -161,6 +166,9 @@ class Agent(nn.Module):
         # policy body: the x-transformers Decoder (x_transformers_rl.py) or the per-timestep causal
         # fractal encoder (fractal_rl.py:349-619 made causal, fractal.FractalPolicyActorCritic)
         if policy_body == 'fractal':
+            if c.attn_window:
+                raise NotImplementedError('the fractal policy body has no sliding window: set attn_max_attend_past '
+                                          'to None')
             if c.gate_values or c.value_residual or c.ff_no_bias or c.ff_glu or c.qk_norm or c.rotary_xpos or c.rms_norm:
                 raise NotImplementedError('the fractal policy body has no gated values / value residual / bias-free or '
                                           'GLU feed-forward / qk norm / xPos rotary / RMSNorm: set attn_gate_values / '

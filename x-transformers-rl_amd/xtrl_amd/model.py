@@ -52,6 +52,7 @@ class ModelConfig:
     qk_norm_scale: float = 10.           # x-transformers attn_qk_norm_scale
     rotary_xpos: bool = False            # x-transformers rotary_xpos: xPos-scaled rotary (q x s^p, k / s^p)
     xpos_scale_base: float = 512.        # x-transformers rotary_xpos_scale_base
+    attn_window: int = 0                 # x-transformers attn_max_attend_past: key j visible iff 0 <= i - j <= W (0: none)
     rotary_abs_rollout: bool = False     # decision log: reference semantics = rotary position 0 in rollout
     hl_reduction_mean: bool = True       # decision log: hl-gauss-pytorch default reduction
     hl_sigma_ratio: float = 2.0
@@ -353,7 +354,7 @@ class WorldModelActorCritic(nn.Module):
                 q, k = F.normalize(q, dim=-1), F.normalize(k, dim=-1)
             q = torch.cat((q[..., :rot] * cos * xq + _rotate_half(q[..., :rot]) * sin * xq, q[..., rot:]), dim=-1)
             k = torch.cat((k[..., :rot] * cos * xk + _rotate_half(k[..., :rot]) * sin * xk, k[..., rot:]), dim=-1)
-            o = ops.attention(q, k, v, lens, scale, p_drop, attn_seed, attn_offset, li)
+            o = ops.attention(q, k, v, lens, scale, p_drop, attn_seed, attn_offset, li, window=c.attn_window)
             o = o.permute(0, 2, 1, 3).reshape(b, n, I)
             if gate_pre is not None:
                 o = o * gate_pre.sigmoid()

@@ -212,7 +212,7 @@ class AttentionFn(torch.autograd.Function):
     """softmax(q k^T * scale + causal/key-padding mask) with post-softmax dropout, times v."""
 
     @staticmethod
-    def forward(ctx, q, k, v, lens, scale, dropout_p, seed, offset, sub):
+    def forward(ctx, q, k, v, lens, scale, dropout_p, seed, offset, sub, window=0):
         lib = L.lib()
         b, H, n, dh = q.shape
         for t in (q, k, v):
@@ -221,32 +221,33 @@ class AttentionFn(torch.autograd.Function):
         assert lens.dtype == torch.int32 and lens.shape == (b,)
         o = torch.empty_like(q)
         lse = torch.empty(b, H, n, device=q.device, dtype=torch.float32)
-        L.check(lib.xtrl_attn_fwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), b, H, n, dh,
-                                  float(scale), float(dropout_p), int(seed), int(offset), int(sub), L.stream()),
-                'attn_fwd')
+        L.check(lib.xtrl_attn_fwd_win(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), b, H, n, dh,
+                                      float(scale), float(dropout_p), int(seed), int(offset), int(sub), int(window),
+                                      L.stream()), 'attn_fwd')
         ctx.save_for_backward(q, k, v, lens, o, lse)
-        ctx.cfg = (float(scale), float(dropout_p), int(seed), int(offset), int(sub))
+        ctx.cfg = (float(scale), float(dropout_p), int(seed), int(offset), int(sub), int(window))
         return o
 
     @staticmethod
     def backward(ctx, do):
         lib = L.lib()
         q, k, v, lens, o, lse = ctx.saved_tensors
-        scale, p, seed, offset, sub = ctx.cfg
+        scale, p, seed, offset, sub, window = ctx.cfg
         b, H, n, dh = q.shape
         do = do.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         delta = torch.empty(b, H, n, device=q.device, dtype=torch.float32)
-        L.check(lib.xtrl_attn_bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do),
-                                  L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(delta), b, H, n, dh, scale, p, seed, offset,
-                                  sub, L.stream()), 'attn_bwd')
-        return dq, dk, dv, None, None, None, None, None, None
+        L.check(lib.xtrl_attn_bwd_win(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do),
+                                      L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(delta), b, H, n, dh, scale, p, seed,
+                                      offset, sub, window, L.stream()), 'attn_bwd')
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
-def attention(q, k, v, lens, scale, dropout_p=0., seed=0, offset=0, sub=0):
-    """``offset`` / ``sub``: the dropout stream (Philox c2 base and c3 sub-index = decoder layer)."""
+def attention(q, k, v, lens, scale, dropout_p=0., seed=0, offset=0, sub=0, window=0):
+    """``offset`` / ``sub``: the dropout stream (Philox c2 base and c3 sub-index = decoder layer);
+    ``window`` > 0: query i sees key j only if i - j <= window (x-transformers max_attend_past)."""
     return AttentionFn.apply(q.contiguous(), k.contiguous(), v.contiguous(), lens, scale, dropout_p, seed, offset,
-                             sub)
+                             sub, window)
 
 
 # --------------------------------------------------------------------------------------------

@@ -167,6 +167,7 @@ class RolloutEngine:
         D.qk_norm, D.attn_scale = int(qk), float(c.qk_norm_scale) if qk else 0.
         D.xpos_base = float(c.xpos_scale_base) if getattr(c, 'rotary_xpos', False) else 0.
         D.rms_norm = int(getattr(c, 'rms_norm', False))
+        D.attn_window = int(getattr(c, 'attn_window', 0))   # sliding window (0: none)
         D.sim_mode, D.hazard_log2, D.rs_eps = self.sim_mode, hazard_log2, 1e-5
         if clamp is not None:
             D.clamp_lo, D.clamp_hi, D.has_clamp = float(clamp[0]), float(clamp[1]), 1
@@ -675,6 +676,7 @@ class FractalRolloutEngine(RolloutEngine):
     def _build_desc(self, clamp, hazard_log2):
         super()._build_desc(clamp, hazard_log2)
         self.desc.state_only = 1
+        self.desc.attn_window = 0   # (the fractal body has no sliding window)
         Lv = self.levels
         levels = (L.FractalLevel * Lv)()
         names = [n for n, _ in L.FractalLevel._fields_]

@@ -165,6 +165,7 @@ class FusedTrainStep:
         _heads_desc(D, c, flat)
         D.ln_final = off('transformer.attn_layers.final_norm.' + nw)
         D.rms_norm = int(c.rms_norm)
+        D.attn_window = int(c.attn_window)   # sliding window (0: none)
         D.inv_freq = self.inv_freq.data_ptr()
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
@@ -352,6 +353,7 @@ class FractalTrainStep(FusedTrainStep):
         D.w_pin = off(enc + 'input_embed.weight')
         _heads_desc(D, c, flat)
         D.ln_final = -1
+        D.attn_window = 0   # (the fractal body has no sliding window)
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
         D.part_floats = self.buf['part'].numel()
