@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 22
+#define XTRL_ABI_VERSION 23
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -84,7 +84,8 @@ typedef struct XtrlDecodeLayer {
   const float* ln_attn;  /* [d]  pre-attention LayerNorm gamma */
   /* decode GEMM weights (w_qkv, w_out, w_ff1, w_ff2, w_h1, w_h2) are fragment-packed (xtrl_dgemm_pack)
    * images of the nn.Linear weights described */
-  const float* w_qkv;    /* [n_qkv][d]  rows: to_q | to_k | to_v | to_v_gate (opt) | value-residual mix (opt) */
+  const float* w_qkv;    /* [n_qkv][d]  rows: to_q [I] | to_k [Ikv] | to_v [Ikv] | to_v_gate [I] (opt) | value-residual mix [Hkv] (opt);
+                            I = H dh, Ikv = Hkv dh */
   const float* b_qkv;    /* [n_qkv]     zeros for q/k/v */
   const float* w_out;    /* [d][I]      to_out */
   const float* ln_ff;    /* [d] */
@@ -92,8 +93,8 @@ typedef struct XtrlDecodeLayer {
   const float* b_ff1;    /* [ff] */
   const float* w_ff2;    /* [d][ff] */
   const float* b_ff2;    /* [d] */
-  float* k_cache;        /* [E][H][Tmax][dh]  keys (post-rotary) */
-  float* v_cache;        /* [E][H][Tmax][dh]  values (post value-residual mix) */
+  float* k_cache;        /* [E][Hkv][Tmax][dh]  keys (post-rotary); Hkv = XtrlDecodeDesc.Hkv kv heads (= H without GQA) */
+  float* v_cache;        /* [E][Hkv][Tmax][dh]  values (post value-residual mix) */
   const float* w_out_t;  /* [I][d]  to_out transposed (plain fp32), or NULL: when set (and the shape
                             allows) the attention kernel applies the out-projection + residual
                             itself, x += W_out o, and no out-projection GEMM runs */
@@ -177,7 +178,7 @@ typedef struct XtrlDecodeDesc {
   float* hff;    /* [E][max(ff or 2 ff with ff_glu, 4d)] */
   float* ac_in;  /* [E][in_dim]  (final-normed embed | state embed | latent embed) */
   float* logits; /* [E][A or 2A] */
-  float* v1;     /* [E][I] first layer's values (value residual) */
+  float* v1;     /* [E][Ikv] first layer's values (value residual), per kv head */
   float* xn;     /* [E][d] or NULL: LayerNorm(x) * gain of the next projection, written by the kernel
                     that completes the row (the embedding for layer 0's q|k|v, the fused attention
                     for FF1), so that projection runs without a LayerNorm prologue */
@@ -235,8 +236,14 @@ typedef struct XtrlDecodeDesc {
   void* act_host;
   /* world_model['attn_max_attend_past'] (x-transformers Attention max_attend_past; ABI 22): the step-t
    * query attends the cached keys j with t - j <= attn_window only (at most attn_window + 1 keys; the
-   * cache keeps its [E][H][Tmax][dh] layout, the saving is in reads).  0: no window */
+   * cache keeps its [E][Hkv][Tmax][dh] layout, the saving is in reads).  0: no window */
   int attn_window;
+  /* Agent(kv_heads=Hkv) / world_model['attn_one_kv_head'] (x-transformers Attention kv_heads, grouped-query
+   * attention; ABI 23): k and v have Hkv heads, H % Hkv == 0, and query head h reads kv head h % Hkv.
+   * n_qkv = I + 2 Ikv (+ I gate) (+ Hkv mix) with Ikv = Hkv dh; the caches are [E][Hkv][Tmax][dh] and v1
+   * [E][Ikv]: the resident cache and the cache read shrink by H / Hkv.  0: Hkv = H (a zero-initialised
+   * descriptor is plain multi-head attention) */
+  int Hkv;
 } XtrlDecodeDesc;
 
 /* Reset: state_0 = sim reset, prev_action = -1 / 0, prev_reward = 0, alive = 1, lens = 0, and
@@ -439,6 +446,27 @@ int xtrl_attn_bwd_part_win(const float* q, const float* k, const float* v, const
                            const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
                            float* dq_part, int64_t dq_part_floats, int b, int H, int n, int dh, float scale,
                            float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, int window, void* stream);
+/* The three _win entry points with grouped-query attention (x-transformers Attention kv_heads; ABI 23):
+ * q, dout, o, dq are [b][H][n][dh] and k, v, dk, dv [b][Hkv][n][dh], 1 <= Hkv <= H, H % Hkv == 0.  Query
+ * head h reads kv head h % Hkv (x-transformers repeats k / v as 'b kvh n d -> b (r kvh) n d'); dk / dv of
+ * a kv head are the sums over its H / Hkv query heads, taken in ascending head order inside one
+ * workgroup (no atomics: the same bits every run).  lse and delta_ws stay [b][H][n], the dropout keep
+ * bits stay keyed by the query head (c2 = offset + b * H + h: the masks do not depend on Hkv), and
+ * dq_part stays xtrl_attn_bwd_part_floats(b, H, n, dh) floats (the dQ partials are per query head).
+ * Hkv = H: the _win entry points (which are these with Hkv = H), the same kernels bit for bit.
+ * Hkv < H has no one-launch fused backward: n <= 128 runs the kernel pair (xtrl_attn_bwd_gqa) or the
+ * partial-workspace form (xtrl_attn_bwd_part_gqa). */
+int xtrl_attn_fwd_gqa(const float* q, const float* k, const float* v, const int32_t* lens, float* o, float* lse,
+                      int b, int H, int Hkv, int n, int dh, float scale, float dropout_p, uint64_t seed,
+                      uint32_t offset, uint32_t sub, int window, void* stream);
+int xtrl_attn_bwd_gqa(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                      const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws, int b,
+                      int H, int Hkv, int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset,
+                      uint32_t sub, int window, void* stream);
+int xtrl_attn_bwd_part_gqa(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                           const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                           float* dq_part, int64_t dq_part_floats, int b, int H, int Hkv, int n, int dh, float scale,
+                           float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, int window, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Learn-step forward / backward of WorldModelActorCritic on one minibatch, hand-scheduled (no
@@ -459,7 +487,7 @@ int xtrl_attn_bwd_part_win(const float* q, const float* k, const float* v, const
  * ------------------------------------------------------------------------------------------- */
 typedef struct XtrlTrainLayer {
   int64_t ln_attn, w_proj, b_proj, w_out, ln_ff, w_ff1, b_ff1, w_ff2, b_ff2;
-  int n_qkv;            /* 3I (+ I value gates) (+ H value-residual mix, layers >= 2) */
+  int n_qkv;            /* I + 2 Ikv (+ I value gates) (+ Hkv value-residual mix, layers >= 2); Ikv = Hkv dh (XtrlTrainDesc.Hkv) */
   int mix;              /* learned value-residual mix in this layer */
   float* x_attn;        /* [T][d] residual stream entering the attention block */
   float* x_ff;          /* [T][d] entering the feed-forward block */
@@ -468,7 +496,7 @@ typedef struct XtrlTrainLayer {
   float* st_attn;       /* [T][2] LayerNorm (mean, rstd) */
   float* st_ff;
   float* proj;          /* [T][n_qkv] q | k | v | gate | mix pre-activations */
-  float* qkv;           /* [T][3I] rotary q, k and (mixed) v */
+  float* qkv;           /* [T][I + 2 Ikv] rotary q, k and (mixed) v */
   float* o;             /* [T][I] attention output */
   float* og;            /* [T][I] gated output (== o when there are no value gates) */
   float* lse;           /* [b][H][n] */
@@ -523,7 +551,7 @@ typedef struct XtrlTrainDesc {
   float* dff;                    /* [T][ff] */
   float* dproj;                  /* [T][max n_qkv] */
   float* dog;                    /* [T][I] */
-  float* dvfirst;                /* [T][I] */
+  float* dvfirst;                /* [T][Ikv] */
   float* dz1;                    /* [T][4d] */
   float* dac;                    /* [T][in_dim] */
   float* dzp;                    /* [T][d + 4] */
@@ -615,6 +643,10 @@ typedef struct XtrlTrainDesc {
   /* world_model['attn_max_attend_past'] (ABI 22): query i attends key j iff j <= i, i - j <= attn_window
    * and j < lens (xtrl_attn_fwd_win / xtrl_attn_bwd_part_win); 0: no window */
   int attn_window;
+  /* grouped-query attention (ABI 23), as XtrlDecodeDesc.Hkv: to_k / to_v give Hkv heads, the
+   * value-residual mix one column per kv head and dvfirst [T][Ikv]; the attention runs as
+   * xtrl_attn_fwd_gqa / xtrl_attn_bwd_part_gqa on the token rows.  0: Hkv = H */
+  int Hkv;
 } XtrlTrainDesc;
 
 int xtrl_train_forward(const XtrlTrainDesc* desc, void* stream);

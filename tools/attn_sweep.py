@@ -11,7 +11,9 @@ timed reps (XtrlDecodeDesc.prof_events) give the event time.  Algorithmic bytes 
 bench.py's DecodeAttnTimer: per live (row, head) the K and V rows 0..t-1 (2 t dh fp32) + the row's
 q|k|v|gate|mix operands + the value-residual row + the K/V append + the output.  ``run --window W`` sets
 XtrlDecodeDesc.attn_window (world_model['attn_max_attend_past']): the step reads the last min(t, W)
-cached keys only, and the bytes count those.
+cached keys only, and the bytes count those.  ``run --kv-heads Hkv`` builds the C3 learner with
+agent_kwargs kv_heads = Hkv: the cache rows, the k | v | mix operands and the value-residual row
+are counted per kv head, q | gate and the output per query head.
 ``summarize`` assigns the k_attn_decode dispatches of a rocprofv3 --kernel-trace (and optional
 --pmc FETCH_SIZE / WRITE_SIZE) run of ``run`` to the points in launch order (the points are run
 in a fixed order, (warm + reps) x L dispatches each) and reports the profiler's duration and the
@@ -24,6 +26,7 @@ import glob
 import json
 import os
 import sys
+import tempfile
 from pathlib import Path
 
 REPO = Path(__file__).resolve().parent.parent
@@ -41,11 +44,31 @@ def points():
 
 def algo_bytes(c, t, R, window=0):
     H, dh = c.heads, c.dim_head
+    Hkv = getattr(c, 'kv_heads', 0) or H   # grouped-query attention: the cache rows, k, v, mix and v1 are per kv head
     if window:
         t = min(t, window)   # cached keys max(0, t - W) .. t - 1
-    row = 3 * dh + (dh if c.gate_values else 0) + (1 if c.learned_mix else 0)
+    kv_row = 2 * dh + (1 if c.learned_mix else 0)           # the row's k | v | mix operands
+    q_row = dh + (dh if c.gate_values else 0)               # q | gate
     vres = dh if c.value_residual else 0
-    return 4.0 * R * H * (2 * t * dh + row + vres + 2 * dh + dh)
+    return 4.0 * R * (Hkv * (2 * t * dh + kv_row + vres + 2 * dh) + H * (q_row + dh))
+
+
+def build_c3(cfg, kv_heads):
+    """bench.build_learner's C3 learner; ``kv_heads`` > 0: the same with agent_kwargs kv_heads."""
+    import bench
+    if not kv_heads:
+        return bench.build_learner(cfg, 0, use_graph=False)
+    from xtrl_amd import Learner, SynthVecSim
+    wm = dict(attn_dim_head=cfg['dim_head'], heads=cfg['heads'], depth=cfg['depth'], attn_gate_values=True,
+              add_value_residual=True, learned_value_residual_mix=True)
+    learner = Learner(state_dim=cfg['S'], num_actions=cfg['A'], reward_range=(-5., 5.), world_model=wm,
+                      max_timesteps=cfg['T'], batch_size=cfg['batch'], num_episodes_per_update=cfg['episodes'],
+                      evolutionary=cfg['evo'], evolve_every=5, evolve_after_step=10,
+                      latent_gene_pool=dict(dim=32, num_genes_per_island=3, num_selected=2, tournament_size=2),
+                      agent_kwargs=dict(hidden_dim=cfg['dim'], dropout=cfg['dropout'], seed=0, kv_heads=kv_heads,
+                                        save_path=os.path.join(tempfile.gettempdir(), 'xtrl_attn_sweep_ppo.pt')),
+                      use_graph=False)
+    return learner, SynthVecSim(cfg['S'], cfg['A'], cfg['mode'], cfg['hazard_log2'])
 
 
 def run(a):
@@ -53,7 +76,7 @@ def run(a):
     import bench
     cfg = dict(bench.CONFIGS['c3'], T=512)
     torch.manual_seed(0)
-    learner, env = bench.build_learner(cfg, 0, use_graph=False)
+    learner, env = build_c3(cfg, a.kv_heads)
     learner.rollout_device(env, 0, 512)      # packs the weights, fills the caches
     torch.cuda.synchronize()
     eng = learner._engine_for(env, 512)
@@ -80,10 +103,11 @@ def run(a):
         eng.desc.prof_events = None
         us = ms * 1e3 / (a.reps * L)
         b = algo_bytes(c, t, R, a.window)
-        out.append(dict(t=t, rows=R, window=a.window, us_event=round(us, 2), bytes=b, gbs_event=round(b / us / 1e3, 1),
+        out.append(dict(t=t, rows=R, window=a.window, kv_heads=a.kv_heads or c.heads, us_event=round(us, 2), bytes=b, gbs_event=round(b / us / 1e3, 1),
                         frac_event=round(b / us / 1e3 / HBM, 4)))
         print(json.dumps(out[-1]), flush=True)
-    json.dump(dict(points=out, reps=a.reps, warm=WARM, layers=L, window=a.window), open(a.out, 'w'), indent=1)
+    json.dump(dict(points=out, reps=a.reps, warm=WARM, layers=L, window=a.window, kv_heads=a.kv_heads or c.heads),
+              open(a.out, 'w'), indent=1)
 
 
 def summarize(a):
@@ -133,6 +157,8 @@ if __name__ == '__main__':
     r = sub.add_parser('run')
     r.add_argument('--reps', type=int, default=10)
     r.add_argument('--window', type=int, default=0, help='sliding window (attn_max_attend_past); 0: none')
+    r.add_argument('--kv-heads', type=int, default=0,
+                   help='grouped-query attention (agent_kwargs kv_heads); 0: multi-head, bench.py\'s C3 learner')
     r.add_argument('--out', default=str(REPO / 'gpurun_out' / 'attn_sweep.json'))
     s = sub.add_parser('summarize')
     s.add_argument('json')

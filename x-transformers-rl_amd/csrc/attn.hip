@@ -57,6 +57,10 @@ struct AttnArgs {
   uint32_t c3;        // rng_c3(FIELD_DROPOUT, layer); byte mode: rng_c3(FIELD_DROPOUT, layer | 1 << 23)
   int causal;
   int window;         // sliding window W: key j visible to query i only if i - j <= W (NO_WINDOW: none)
+  // grouped-query attention (read by the GQA = true instantiations only): K, V in layout kv and dK, dV
+  // in layout kvgrad hold Hkv heads; query head h reads kv head kv_head_of(h, Hkv)
+  int Hkv;
+  AttnLayout kv, kvgrad;
 };
 constexpr int NO_WINDOW = 1 << 30;   // (i - j <= NO_WINDOW always holds; band tile ranges become the causal ones)
 
@@ -66,7 +70,8 @@ __device__ __forceinline__ int64_t ebase(const AttnArgs& a, const AttnLayout& L,
 }
 
 // ---------------------------------------------------------------------------------------------
-template <int DH>
+// GQA = true (Hkv < H): the K / V base is the kv head's, in its own layout; nothing else changes
+template <int DH, bool GQA = false>
 __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Ks[TK][KST], Vs[TK][KST];
@@ -80,6 +85,8 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
   if (q0 >= n) return;   // (packed rows: a query tile past the episode; workgroup-uniform)
   const int64_t ib = ebase(a, a.in, b) + h * a.in.sh, ob = ebase(a, a.out, b) + h * a.out.sh;
   const int isi = a.in.si, osi = a.out.si;
+  const int64_t kb = GQA ? ebase(a, a.kv, b) + kv_head_of(h, a.Hkv) * a.kv.sh : ib;
+  const int ksi = GQA ? a.kv.si : isi;
   const int lr = lane & 15, lg = lane >> 4;
   const uint32_t off = a.offset + (uint32_t)bh;
 
@@ -107,8 +114,8 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
     __syncthreads();
     for (int x = tid; x < TK * DH; x += 256) {
       const int j = x / DH, c = x - j * DH, jj = kt * TK + j;
-      Ks[j][c] = jj < n ? a.K[ib + (int64_t)jj * isi + c] : 0.f;
-      Vs[j][c] = jj < n ? a.V[ib + (int64_t)jj * isi + c] : 0.f;
+      Ks[j][c] = jj < n ? a.K[kb + (int64_t)jj * ksi + c] : 0.f;
+      Vs[j][c] = jj < n ? a.V[kb + (int64_t)jj * ksi + c] : 0.f;
     }
     __syncthreads();
     f32x4v sacc[4];
@@ -204,8 +211,14 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
 // WIN = false (dh = 16 without a window, the C2 / C3 shapes): the window tests are compiled out — with
 // them the 128-register budget of the 4-waves-per-SIMD form spilled 2 registers; every other form
 // takes the window at run time (NO_WINDOW: none)
-template <int DH, bool DQ = false, bool WIN = true>
+// GQA = true (Hkv < H, always with WIN): the grid is (key tile, b Hkv); the workgroup holds its kv
+// head's key tile and walks the query heads h of the group (kv_head_of(h, Hkv) == its kv head) in
+// ascending order, each over its query tiles as before, adding into the same dK / dV registers — a
+// fixed summation order, no atomics.  D, the dQ partials and the keep bits stay per query head.
+// GQA = false: one pass with h = the grid's head, the code of before
+template <int DH, bool DQ = false, bool WIN = true, bool GQA = false>
 __global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_attn_bwd_dkdv(const AttnArgs a) {
+  static_assert(WIN || !GQA, "the GQA forms take the window at run time");
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Qs[TQ][KST], dOs[TQ][KST];
   __shared__ float Ks[DQ ? TK : 1][KST];
@@ -215,23 +228,31 @@ __global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_a
   // 3, and a quarter of the C3 grid ran as a second round), so the C3 grid is one round
   __shared__ float Ps[4][16][PST];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, tid = threadIdx.x;
-  const int bh = blockIdx.y, b = bh / a.H, ns = a.n;
+  // the grid's head hk: the kv head (GQA) or the query head, which is its own kv head
+  const int nhk = GQA ? a.Hkv : a.H;
+  const int b = blockIdx.y / nhk, ns = a.n;
   const int j0 = blockIdx.x * TK;
   const int len = a.lens[b];
   const int n = a.ep_off ? min(len, ns) : ns;   // packed rows: the episode's own length
-  const int h = bh - b * a.H;
-  const int64_t ib = ebase(a, a.in, b) + h * a.in.sh, ob = ebase(a, a.out, b) + h * a.out.sh, gb = ebase(a, a.grad, b) + h * a.grad.sh;
+  const int hk = blockIdx.y - b * nhk;
+  // the query head at work: the grid's own (GQA: set per pass of the group loop below)
+  int bh = blockIdx.y, h = hk;
+  int64_t ib = ebase(a, a.in, b) + h * a.in.sh, ob = ebase(a, a.out, b) + h * a.out.sh, gb = ebase(a, a.grad, b) + h * a.grad.sh;
   const int isi = a.in.si, osi = a.out.si, gsi = a.grad.si;
   const int lr = lane & 15, lg = lane >> 4;
-  const uint32_t off = a.offset + (uint32_t)bh;
+  uint32_t off = a.offset + (uint32_t)bh;
+  // K, V and dK, dV of head hk (GQA: in their own layouts)
+  const int64_t kb = GQA ? ebase(a, a.kv, b) + hk * a.kv.sh : ib;
+  const int64_t kgb = GQA ? ebase(a, a.kvgrad, b) + hk * a.kvgrad.sh : gb;
+  const int ksi = GQA ? a.kv.si : isi, kgsi = GQA ? a.kvgrad.si : gsi;
 
   float ka[KS], va[KS];
   {
     const int j = j0 + 16 * w + lr;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      ka[s] = (j < n) ? a.K[ib + (int64_t)j * isi + 4 * s + lg] : 0.f;
-      va[s] = (j < n) ? a.V[ib + (int64_t)j * isi + 4 * s + lg] : 0.f;
+      ka[s] = (j < n) ? a.K[kb + (int64_t)j * ksi + 4 * s + lg] : 0.f;
+      va[s] = (j < n) ? a.V[kb + (int64_t)j * ksi + 4 * s + lg] : 0.f;
     }
   }
   f32x4v dk[ND], dv[ND];
@@ -244,153 +265,171 @@ __global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_a
   if constexpr (DQ) {
     for (int x = tid; x < TK * DH; x += 256) {
       const int j = x / DH, c = x - j * DH, jj = j0 + j;
-      Ks[j][c] = jj < n ? a.K[ib + (int64_t)jj * isi + c] : 0.f;
+      Ks[j][c] = jj < n ? a.K[kb + (int64_t)jj * ksi + c] : 0.f;
     }
-    if (j0 == 0 && len <= 0) {   // no valid key: the rows' dQ is 0, this workgroup its only writer
+    if (!GQA && j0 == 0 && len <= 0) {   // no valid key: the rows' dQ is 0, this workgroup its only writer
       for (int x = tid; x < n * DH; x += 256) {
         const int i = x / DH, c = x - i * DH;
         a.dQ[gb + (int64_t)i * gsi + c] = 0.f;
       }
     }
   }
-  // a key tile without a valid key (a tile of padded rows) under WIN: its workgroup still owns the D
-  // of its own query tile — it stages that one tile, stores D (the very same sum) and stops there
-  // (without a window the key-tile-0 workgroup visits every query tile and stays the owner, as it
-  // always was: no extra staging)
-  const bool live = j0 < len;
-  const bool own0 = !WIN || a.window == NO_WINDOW;
-  if (live || (!own0 && len > 0)) {
-    // query tiles of the band: from the diagonal to the last one holding a row <= j0 + TK - 1 + W
-    const int n_end = !WIN ? n : (live ? min(n, j0 + TK + a.window) : min(n, j0 + TQ));
-    for (int qt = j0 / TQ; qt * TQ < n_end; ++qt) {
-      __syncthreads();
-      for (int x = tid; x < TQ * DH; x += 256) {
-        const int i = x / DH, c = x - i * DH, ii = qt * TQ + i;
-        Qs[i][c] = ii < n ? a.Q[ib + (int64_t)ii * isi + c] : 0.f;
-        dOs[i][c] = ii < n ? a.dO[ob + (int64_t)ii * osi + c] : 0.f;
-      }
-      // D_i = rowsum(dO_i * O_i) of the tile's query rows, computed here (the O row in registers
-      // while the tile stages) in the order of a sequential sum over the head dimension; the
-      // diagonal workgroup (key tile == query tile: a row always sees itself, so a window never
-      // skips the pair) stores it for k_attn_bwd_dq
-      float orow[DH];
-      if (tid < TQ) {
-        const int ii = qt * TQ + tid;
-        Ls[tid] = ii < n ? a.LSE[(int64_t)bh * ns + ii] : 0.f;
-#pragma unroll
-        for (int c = 0; c < DH; ++c) orow[c] = ii < n ? a.O[ob + (int64_t)ii * osi + c] : 0.f;
-      }
-      __syncthreads();
-      if (tid < TQ) {
-        const int ii = qt * TQ + tid;
-        float dsum = 0.f;
-#pragma unroll
-        for (int c = 0; c < DH; ++c) dsum += dOs[tid][c] * orow[c];
-        Dls[tid] = dsum;
-        if ((own0 ? j0 == 0 : qt * TQ == j0) && ii < n) a.Dout[(int64_t)bh * ns + ii] = dsum;
-      }
-      if (WIN && !live) break;   // (workgroup-uniform)
-      __syncthreads();
-      float dsr[4][4];
-#pragma unroll
-      for (int sub = 0; sub < 4; ++sub) {
-        f32x4v st = f32x4v{0.f, 0.f, 0.f, 0.f}, dpt = f32x4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          st = mfma16(ka[s], Qs[16 * sub + lr][4 * s + lg], st);
-          dpt = mfma16(va[s], dOs[16 * sub + lr][4 * s + lg], dpt);
+  int g = 0;   // GQA: the query heads, ascending; one pass each for those of this kv head
+  do {
+    if constexpr (GQA) {
+      while (g < a.H && kv_head_of(g, a.Hkv) != hk) ++g;   // (workgroup-uniform) the next query head of kv head hk
+      if (g >= a.H) break;
+      h = g;
+      bh = b * a.H + h;
+      ib = ebase(a, a.in, b) + h * a.in.sh, ob = ebase(a, a.out, b) + h * a.out.sh, gb = ebase(a, a.grad, b) + h * a.grad.sh;
+      off = a.offset + (uint32_t)bh;
+      if (DQ && j0 == 0 && len <= 0) {   // (as above, per query head)
+        for (int x = tid; x < n * DH; x += 256) {
+          const int i = x / DH, c = x - i * DH;
+          a.dQ[gb + (int64_t)i * gsi + c] = 0.f;
         }
-        const int il = 16 * sub + lr, i = qt * TQ + il;
-        // keep words of row i at key columns j0 + 16 w + 4 lg + 0..3: the four lanes of a quad hold
-        // rows 4 (i >> 2) + 0..3; lane c computes the block of column 4 lg + c (its four words are
-        // the quad's four rows) and a quad transpose hands every lane its row's word of each column
-        // (byte mode: lane c computes the block of column class 4 lg + c, takes word w — this wave's
-        // 16-column group — and the quad transpose deals byte (row & 3) of each column's word)
-        uint32_t kq[4] = {0u, 0u, 0u, 0u};
-        if (a.thresh8) {
-          const u32x4_t kb = philox4x32_10((uint32_t)(i >> 2), (uint32_t)((j0 >> 6) * 16 + 4 * lg + (lr & 3)), off,
-                                           a.c3, a.seed);
-          const uint32_t wd = qword(kb, w);
-#pragma unroll
-          for (int c = 0; c < 4; ++c) kq[c] = (wd >> (8 * c)) & 0xFFu;
-          quad_transpose(kq, lane);
-        } else if (a.thresh) {
-          const u32x4_t kb = philox4x32_10((uint32_t)(i >> 2), (uint32_t)(j0 + 16 * w + 4 * lg + (lr & 3)), off,
-                                           a.c3, a.seed);
-          kq[0] = kb.x;
-          kq[1] = kb.y;
-          kq[2] = kb.z;
-          kq[3] = kb.w;
-          quad_transpose(kq, lane);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int j = j0 + 16 * w + 4 * lg + r;
-          // 0 <= i - j <= W in one compare
-          const bool ok = (WIN ? (unsigned)(i - j) <= (unsigned)a.window : j <= i) && (j < len) && (i < n);
-          const float p = ok ? expf(st[r] * a.scale - Ls[il]) : 0.f;
-          float z = 1.f;
-          if (a.thresh8 && ok) z = (kq[r] >= a.thresh8) ? a.inv_keep : 0.f;
-          else if (a.thresh && ok) z = (kq[r] >= a.thresh) ? a.inv_keep : 0.f;
-          Ps[w][4 * lg + r][il] = p * z;
-          dsr[sub][r] = p * (dpt[r] * z - Dls[il]);
-        }
-      }
-      wave_sync();
-#pragma unroll
-      for (int d = 0; d < ND; ++d)
-#pragma unroll
-        for (int s = 0; s < TQ / 4; ++s) dv[d] = mfma16(Ps[w][lr][4 * s + lg], dOs[4 * s + lg][16 * d + lr], dv[d]);
-      wave_sync();
-#pragma unroll
-      for (int sub = 0; sub < 4; ++sub)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Ps[w][4 * lg + r][16 * sub + lr] = dsr[sub][r];
-      wave_sync();
-#pragma unroll
-      for (int d = 0; d < ND; ++d)
-#pragma unroll
-        for (int s = 0; s < TQ / 4; ++s) dk[d] = mfma16(Ps[w][lr][4 * s + lg], Qs[4 * s + lg][16 * d + lr], dk[d]);
-      if constexpr (DQ) {
-        __syncthreads();   // every wave's dS image of the pair is in LDS
-        // dQ rows 16 w .. 16 w + 15 of this query tile: dS[query][key] = image [key / 16][key % 16][query]
-        f32x4v dq[ND];
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-          dq[d] = f32x4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int s = 0; s < TK / 4; ++s) {
-            const int j = 4 * s + lg;
-            dq[d] = mfma16(Ps[j >> 4][j & 15][16 * w + lr], Ks[j][16 * d + lr], dq[d]);
-          }
-        }
-        // the key tiles visiting this query tile: max(0, qt TQ - W) / TK .. min(qt, kmax); one: dQ directly
-        const bool sole = (WIN ? max(0, qt * TQ - a.window) / TK : 0) == min(qt, kmax);
-        const int64_t pb = ((int64_t)blockIdx.x * gridDim.y + bh) * ns;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = qt * TQ + 16 * w + 4 * lg + r;
-          if (i < n) {
-#pragma unroll
-            for (int d = 0; d < ND; ++d) {
-              if (sole) a.dQ[gb + (int64_t)i * gsi + 16 * d + lr] = dq[d][r] * a.scale;
-              else a.dQp[(pb + i) * DH + 16 * d + lr] = dq[d][r];
-            }
-          }
-        }
-      } else {
-        wave_sync();
       }
     }
-  }
+    // a key tile without a valid key (a tile of padded rows) under WIN: its workgroup still owns the D
+    // of its own query tile — it stages that one tile, stores D (the very same sum) and stops there
+    // (without a window the key-tile-0 workgroup visits every query tile and stays the owner, as it
+    // always was: no extra staging)
+    const bool live = j0 < len;
+    const bool own0 = !WIN || a.window == NO_WINDOW;
+    if (live || (!own0 && len > 0)) {
+      // query tiles of the band: from the diagonal to the last one holding a row <= j0 + TK - 1 + W
+      const int n_end = !WIN ? n : (live ? min(n, j0 + TK + a.window) : min(n, j0 + TQ));
+      for (int qt = j0 / TQ; qt * TQ < n_end; ++qt) {
+        __syncthreads();
+        for (int x = tid; x < TQ * DH; x += 256) {
+          const int i = x / DH, c = x - i * DH, ii = qt * TQ + i;
+          Qs[i][c] = ii < n ? a.Q[ib + (int64_t)ii * isi + c] : 0.f;
+          dOs[i][c] = ii < n ? a.dO[ob + (int64_t)ii * osi + c] : 0.f;
+        }
+        // D_i = rowsum(dO_i * O_i) of the tile's query rows, computed here (the O row in registers
+        // while the tile stages) in the order of a sequential sum over the head dimension; the
+        // diagonal workgroup (key tile == query tile: a row always sees itself, so a window never
+        // skips the pair) stores it for k_attn_bwd_dq
+        float orow[DH];
+        if (tid < TQ) {
+          const int ii = qt * TQ + tid;
+          Ls[tid] = ii < n ? a.LSE[(int64_t)bh * ns + ii] : 0.f;
+#pragma unroll
+          for (int c = 0; c < DH; ++c) orow[c] = ii < n ? a.O[ob + (int64_t)ii * osi + c] : 0.f;
+        }
+        __syncthreads();
+        if (tid < TQ) {
+          const int ii = qt * TQ + tid;
+          float dsum = 0.f;
+#pragma unroll
+          for (int c = 0; c < DH; ++c) dsum += dOs[tid][c] * orow[c];
+          Dls[tid] = dsum;
+          if ((own0 ? j0 == 0 : qt * TQ == j0) && ii < n) a.Dout[(int64_t)bh * ns + ii] = dsum;
+        }
+        if (WIN && !live) break;   // (workgroup-uniform)
+        __syncthreads();
+        float dsr[4][4];
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub) {
+          f32x4v st = f32x4v{0.f, 0.f, 0.f, 0.f}, dpt = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int s = 0; s < KS; ++s) {
+            st = mfma16(ka[s], Qs[16 * sub + lr][4 * s + lg], st);
+            dpt = mfma16(va[s], dOs[16 * sub + lr][4 * s + lg], dpt);
+          }
+          const int il = 16 * sub + lr, i = qt * TQ + il;
+          // keep words of row i at key columns j0 + 16 w + 4 lg + 0..3: the four lanes of a quad hold
+          // rows 4 (i >> 2) + 0..3; lane c computes the block of column 4 lg + c (its four words are
+          // the quad's four rows) and a quad transpose hands every lane its row's word of each column
+          // (byte mode: lane c computes the block of column class 4 lg + c, takes word w — this wave's
+          // 16-column group — and the quad transpose deals byte (row & 3) of each column's word)
+          uint32_t kq[4] = {0u, 0u, 0u, 0u};
+          if (a.thresh8) {
+            const u32x4_t kb = philox4x32_10((uint32_t)(i >> 2), (uint32_t)((j0 >> 6) * 16 + 4 * lg + (lr & 3)), off,
+                                             a.c3, a.seed);
+            const uint32_t wd = qword(kb, w);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) kq[c] = (wd >> (8 * c)) & 0xFFu;
+            quad_transpose(kq, lane);
+          } else if (a.thresh) {
+            const u32x4_t kb = philox4x32_10((uint32_t)(i >> 2), (uint32_t)(j0 + 16 * w + 4 * lg + (lr & 3)), off,
+                                             a.c3, a.seed);
+            kq[0] = kb.x;
+            kq[1] = kb.y;
+            kq[2] = kb.z;
+            kq[3] = kb.w;
+            quad_transpose(kq, lane);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int j = j0 + 16 * w + 4 * lg + r;
+            // 0 <= i - j <= W in one compare
+            const bool ok = (WIN ? (unsigned)(i - j) <= (unsigned)a.window : j <= i) && (j < len) && (i < n);
+            const float p = ok ? expf(st[r] * a.scale - Ls[il]) : 0.f;
+            float z = 1.f;
+            if (a.thresh8 && ok) z = (kq[r] >= a.thresh8) ? a.inv_keep : 0.f;
+            else if (a.thresh && ok) z = (kq[r] >= a.thresh) ? a.inv_keep : 0.f;
+            Ps[w][4 * lg + r][il] = p * z;
+            dsr[sub][r] = p * (dpt[r] * z - Dls[il]);
+          }
+        }
+        wave_sync();
+#pragma unroll
+        for (int d = 0; d < ND; ++d)
+#pragma unroll
+          for (int s = 0; s < TQ / 4; ++s) dv[d] = mfma16(Ps[w][lr][4 * s + lg], dOs[4 * s + lg][16 * d + lr], dv[d]);
+        wave_sync();
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) Ps[w][4 * lg + r][16 * sub + lr] = dsr[sub][r];
+        wave_sync();
+#pragma unroll
+        for (int d = 0; d < ND; ++d)
+#pragma unroll
+          for (int s = 0; s < TQ / 4; ++s) dk[d] = mfma16(Ps[w][lr][4 * s + lg], Qs[4 * s + lg][16 * d + lr], dk[d]);
+        if constexpr (DQ) {
+          __syncthreads();   // every wave's dS image of the pair is in LDS
+          // dQ rows 16 w .. 16 w + 15 of this query tile: dS[query][key] = image [key / 16][key % 16][query]
+          f32x4v dq[ND];
+#pragma unroll
+          for (int d = 0; d < ND; ++d) {
+            dq[d] = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < TK / 4; ++s) {
+              const int j = 4 * s + lg;
+              dq[d] = mfma16(Ps[j >> 4][j & 15][16 * w + lr], Ks[j][16 * d + lr], dq[d]);
+            }
+          }
+          // the key tiles visiting this query tile: max(0, qt TQ - W) / TK .. min(qt, kmax); one: dQ directly
+          const bool sole = (WIN ? max(0, qt * TQ - a.window) / TK : 0) == min(qt, kmax);
+          const int64_t BH = GQA ? (int64_t)(gridDim.y / nhk) * a.H : (int64_t)gridDim.y;   // b H: the partials are per query head
+          const int64_t pb = ((int64_t)blockIdx.x * BH + bh) * ns;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int i = qt * TQ + 16 * w + 4 * lg + r;
+            if (i < n) {
+#pragma unroll
+              for (int d = 0; d < ND; ++d) {
+                if (sole) a.dQ[gb + (int64_t)i * gsi + 16 * d + lr] = dq[d][r] * a.scale;
+                else a.dQp[(pb + i) * DH + 16 * d + lr] = dq[d][r];
+              }
+            }
+          }
+        } else {
+          wave_sync();
+        }
+      }
+    }
+  } while (GQA && ++g < a.H);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int j = j0 + 16 * w + 4 * lg + r;
     if (j < n) {
 #pragma unroll
       for (int d = 0; d < ND; ++d) {
-        a.dK[gb + (int64_t)j * gsi + 16 * d + lr] = dk[d][r] * a.scale;
-        a.dV[gb + (int64_t)j * gsi + 16 * d + lr] = dv[d][r];
+        a.dK[kgb + (int64_t)j * kgsi + 16 * d + lr] = dk[d][r] * a.scale;
+        a.dV[kgb + (int64_t)j * kgsi + 16 * d + lr] = dv[d][r];
       }
     }
   }
@@ -432,7 +471,7 @@ __global__ __launch_bounds__(256) void k_attn_dq_reduce(const AttnArgs a, int BH
 }
 
 // ---------------------------------------------------------------------------------------------
-template <int DH>
+template <int DH, bool GQA = false>
 __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Ks[TK][KST], Vs[TK][KST];
@@ -446,6 +485,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
   if (q0 >= n) return;   // (packed rows: a query tile past the episode; workgroup-uniform)
   const int64_t ib = ebase(a, a.in, b) + h * a.in.sh, ob = ebase(a, a.out, b) + h * a.out.sh, gb = ebase(a, a.grad, b) + h * a.grad.sh;
   const int isi = a.in.si, osi = a.out.si, gsi = a.grad.si;
+  const int64_t kb = GQA ? ebase(a, a.kv, b) + kv_head_of(h, a.Hkv) * a.kv.sh : ib;   // the kv head's K / V
+  const int ksi = GQA ? a.kv.si : isi;
   const int lr = lane & 15, lg = lane >> 4;
   const uint32_t off = a.offset + (uint32_t)bh;
 
@@ -473,8 +514,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
     __syncthreads();
     for (int x = tid; x < TK * DH; x += 256) {
       const int j = x / DH, c = x - j * DH, jj = kt * TK + j;
-      Ks[j][c] = jj < n ? a.K[ib + (int64_t)jj * isi + c] : 0.f;
-      Vs[j][c] = jj < n ? a.V[ib + (int64_t)jj * isi + c] : 0.f;
+      Ks[j][c] = jj < n ? a.K[kb + (int64_t)jj * ksi + c] : 0.f;
+      Vs[j][c] = jj < n ? a.V[kb + (int64_t)jj * ksi + c] : 0.f;
     }
     __syncthreads();
     // byte mode: one block per lane and key tile holds all 16 keep bytes of its scores
@@ -714,13 +755,15 @@ __device__ __forceinline__ float keep_scale(const AttnArgs& a, uint32_t off, int
   return 1.f;
 }
 
-template <int DH>
+template <int DH, bool GQA = false>
 __global__ __launch_bounds__(256) void k_attn_dead_fwd(const AttnArgs a) {
   const int c = threadIdx.x % DH, i = blockIdx.x * (256 / DH) + threadIdx.x / DH;
   const int bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H, n = a.n;
   const int len = a.lens[b];
   if (len <= 0 || i >= n || i < len + a.window) return;
-  const int64_t ib = ebase(a, a.in, b) + h * a.in.sh, ob = ebase(a, a.out, b) + h * a.out.sh;
+  const int64_t ob = ebase(a, a.out, b) + h * a.out.sh;
+  const int64_t ib = GQA ? ebase(a, a.kv, b) + kv_head_of(h, a.Hkv) * a.kv.sh : ebase(a, a.in, b) + h * a.in.sh;   // V
+  const int isi = GQA ? a.kv.si : a.in.si;
   const uint32_t off = a.offset + (uint32_t)bh;
   // (the DH lanes of a row each draw the keep factor of one key and hand it round: one Philox
   // block per (row, key), not per channel)
@@ -729,7 +772,7 @@ __global__ __launch_bounds__(256) void k_attn_dead_fwd(const AttnArgs a) {
     const float zm = j0 + c < n ? keep_scale(a, off, i, j0 + c) : 0.f;
     for (int jj = 0; jj < DH; ++jj) {
       const float z = __shfl(zm, jj, DH);
-      if (j0 + jj < n) acc += z * a.V[ib + (int64_t)(j0 + jj) * a.in.si + c];
+      if (j0 + jj < n) acc += z * a.V[ib + (int64_t)(j0 + jj) * isi + c];
     }
   }
   const float ov = acc / (float)n;
@@ -738,27 +781,39 @@ __global__ __launch_bounds__(256) void k_attn_dead_fwd(const AttnArgs a) {
   if (a.OGout) a.OGout[at] = ov * sigmoidf_(a.G[ebase(a, a.gate, b) + h * a.gate.sh + (int64_t)i * a.gate.si + c]);
 }
 
-template <int DH>
+// GQA: the grid is (rows, b Hkv) and the thread adds the parts of its kv head's query heads in ascending
+// order before the one read-modify-write of dV (per query head, several would meet on one kv head's dV)
+template <int DH, bool GQA = false>
 __global__ __launch_bounds__(256) void k_attn_dead_bwd(const AttnArgs a) {
   const int c = threadIdx.x % DH, j = blockIdx.x * (256 / DH) + threadIdx.x / DH;
-  const int bh = blockIdx.y, b = bh / a.H, h = bh - b * a.H, n = a.n;
+  const int nhk = GQA ? a.Hkv : a.H;
+  const int b = blockIdx.y / nhk, hk = blockIdx.y - b * nhk, n = a.n;
   const int len = a.lens[b];
   if (len <= 0 || j >= n) return;
-  const int64_t ob = ebase(a, a.out, b) + h * a.out.sh, gb = ebase(a, a.grad, b) + h * a.grad.sh;
-  const uint32_t off = a.offset + (uint32_t)bh;
+  const int64_t gb = GQA ? ebase(a, a.kvgrad, b) + hk * a.kvgrad.sh : ebase(a, a.grad, b) + hk * a.grad.sh;
+  const int gsi = GQA ? a.kvgrad.si : a.grad.si;
   float acc = 0.f;
-  for (int i0 = len + a.window; i0 < n; i0 += DH) {
-    const float zm = i0 + c < n ? keep_scale(a, off, i0 + c, j) : 0.f;
-    for (int ii = 0; ii < DH; ++ii) {
-      const float z = __shfl(zm, ii, DH);
-      if (i0 + ii < n) acc += z * a.dO[ob + (int64_t)(i0 + ii) * a.out.si + c];
+  for (int g = 0; g < (GQA ? a.H : 1); ++g) {
+    const int h = GQA ? g : hk;
+    if (GQA && kv_head_of(h, a.Hkv) != hk) continue;   // (uniform over the workgroup)
+    const int64_t ob = ebase(a, a.out, b) + h * a.out.sh;
+    const uint32_t off = a.offset + (uint32_t)(b * a.H + h);
+    for (int i0 = len + a.window; i0 < n; i0 += DH) {
+      const float zm = i0 + c < n ? keep_scale(a, off, i0 + c, j) : 0.f;
+      for (int ii = 0; ii < DH; ++ii) {
+        const float z = __shfl(zm, ii, DH);
+        if (i0 + ii < n) acc += z * a.dO[ob + (int64_t)(i0 + ii) * a.out.si + c];
+      }
     }
   }
-  if (len + a.window < n) a.dV[gb + (int64_t)j * a.grad.si + c] += acc / (float)n;
+  if (len + a.window < n) a.dV[gb + (int64_t)j * gsi + c] += acc / (float)n;
 }
 
 // whether a problem can have such rows: a window, the padded layout, and a row n - 1 >= 1 + W
 bool has_dead_rows(const AttnProblem& p) { return p.window > 0 && !p.ep_off && p.window <= p.n - 2; }
+
+// grouped-query attention proper: fewer kv heads than query heads (Hkv = 0 or H: today's kernels)
+bool is_gqa(const AttnProblem& p) { return p.Hkv > 0 && p.Hkv < p.H; }
 
 bool attn_fused_bwd_on() {   // XTRL_ATTN_FUSED_BWD=0: the kernel pair (read per launch: tests flip it)
   const char* e = getenv("XTRL_ATTN_FUSED_BWD");
@@ -789,8 +844,29 @@ int fill_args(AttnArgs& a, const AttnProblem& p) {
   XTRL_REQUIRE(p.window >= 0, "attn: window %d < 0 (0 = no window)", p.window);
   XTRL_REQUIRE(p.window == 0 || p.causal, "attn: a window needs causal attention");
   a.window = p.window > 0 ? min(p.window, NO_WINDOW) : NO_WINDOW;
+  XTRL_REQUIRE(p.Hkv >= 0 && p.Hkv <= p.H && (p.Hkv == 0 || p.H % p.Hkv == 0),
+               "attn: kv heads %d must divide heads %d (0 = heads)", p.Hkv, p.H);
+  const bool gqa = is_gqa(p);
+  a.Hkv = gqa ? p.Hkv : p.H;
+  a.kv = gqa ? p.kv : p.in;
+  a.kvgrad = gqa ? p.kvgrad : p.grad;
   return XTRL_OK;
 }
+
+// dh dispatch of a kernel template with a trailing GQA parameter: <dh, false> for one kv head per query
+// head — the instantiations of before — and <dh, true> for Hkv < H
+#define XTRL_ATTN_LAUNCH_DH(KERNEL, gqa, dh, grid)                                                          \
+  do {                                                                                                      \
+    if (gqa) {                                                                                              \
+      if ((dh) == 16) hipLaunchKernelGGL((KERNEL<16, true>), grid, dim3(256), 0, s, a);                     \
+      else if ((dh) == 32) hipLaunchKernelGGL((KERNEL<32, true>), grid, dim3(256), 0, s, a);                \
+      else hipLaunchKernelGGL((KERNEL<64, true>), grid, dim3(256), 0, s, a);                                \
+    } else {                                                                                                \
+      if ((dh) == 16) hipLaunchKernelGGL((KERNEL<16, false>), grid, dim3(256), 0, s, a);                    \
+      else if ((dh) == 32) hipLaunchKernelGGL((KERNEL<32, false>), grid, dim3(256), 0, s, a);               \
+      else hipLaunchKernelGGL((KERNEL<64, false>), grid, dim3(256), 0, s, a);                               \
+    }                                                                                                       \
+  } while (0)
 
 }  // namespace
 
@@ -807,16 +883,13 @@ int attn_fwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   a.LSEout = lse;
   a.G = gate;
   a.OGout = og;
+  const bool gqa = is_gqa(p);
   dim3 grid((p.n + TQ - 1) / TQ, p.b * p.H);
-  if (p.dh == 16) hipLaunchKernelGGL(k_attn_fwd<16>, grid, dim3(256), 0, s, a);
-  else if (p.dh == 32) hipLaunchKernelGGL(k_attn_fwd<32>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_attn_fwd<64>, grid, dim3(256), 0, s, a);
+  XTRL_ATTN_LAUNCH_DH(k_attn_fwd, gqa, p.dh, grid);
   XTRL_LAUNCHED("attn_fwd");
   if (has_dead_rows(p)) {
     dim3 dgrid((p.n + 256 / p.dh - 1) / (256 / p.dh), p.b * p.H);
-    if (p.dh == 16) hipLaunchKernelGGL(k_attn_dead_fwd<16>, dgrid, dim3(256), 0, s, a);
-    else if (p.dh == 32) hipLaunchKernelGGL(k_attn_dead_fwd<32>, dgrid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_attn_dead_fwd<64>, dgrid, dim3(256), 0, s, a);
+    XTRL_ATTN_LAUNCH_DH(k_attn_dead_fwd, gqa, p.dh, dgrid);
     XTRL_LAUNCHED("attn_dead_fwd");
   }
   return XTRL_OK;
@@ -843,7 +916,24 @@ int attn_bwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   // (D = rowsum(dO * O) is formed inside k_attn_bwd_dkdv, whose diagonal workgroups store it for dq)
   dim3 grid((p.n + TQ - 1) / TQ, p.b * p.H);
   const int64_t part_need = attn_dq_part_floats(p.b, p.H, p.n, p.dh);
-  if (p.dh == 16 && p.n <= FB_MAXN && attn_fused_bwd_on()) {   // short episodes: one fused launch
+  const bool gqa = is_gqa(p);
+  if (gqa) {
+    // Hkv < H: the dK / dV grid is over the kv heads (the group loop); the dQ side stays per query head.
+    // The one-launch fused backward has no group loop: short episodes take the long-episode form when
+    // the caller gave the dQ partial workspace, else the kernel pair
+    dim3 kgrid((p.n + TK - 1) / TK, p.b * p.Hkv);
+    if (p.dh == 16 && p.dq_part && p.dq_part_floats >= part_need && attn_fused_bwd_on()) {
+      a.dQp = p.dq_part;
+      hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, true, true>), kgrid, dim3(256), 0, s, a);
+      const int64_t units = (int64_t)p.b * p.H * p.n * 4;
+      hipLaunchKernelGGL(k_attn_dq_reduce<16>, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, a, p.b * p.H);
+    } else {
+      if (p.dh == 16) hipLaunchKernelGGL((k_attn_bwd_dkdv<16, false, true, true>), kgrid, dim3(256), 0, s, a);
+      else if (p.dh == 32) hipLaunchKernelGGL((k_attn_bwd_dkdv<32, false, true, true>), kgrid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((k_attn_bwd_dkdv<64, false, true, true>), kgrid, dim3(256), 0, s, a);
+      XTRL_ATTN_LAUNCH_DH(k_attn_bwd_dq, true, p.dh, grid);
+    }
+  } else if (p.dh == 16 && p.n <= FB_MAXN && attn_fused_bwd_on()) {   // short episodes: one fused launch
     hipLaunchKernelGGL(k_attn_bwd_fused<16>, dim3(p.b * p.H), dim3(256), 0, s, a);
   } else if (p.dh == 16 && p.dq_part && p.dq_part_floats >= part_need && attn_fused_bwd_on()) {
     // long episodes: dK / dV with the dQ pass folded in (partials for multi-key-tile rows) + their sum
@@ -865,10 +955,8 @@ int attn_bwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   }
   XTRL_LAUNCHED("attn_bwd");
   if (has_dead_rows(p)) {
-    dim3 dgrid((p.n + 256 / p.dh - 1) / (256 / p.dh), p.b * p.H);
-    if (p.dh == 16) hipLaunchKernelGGL(k_attn_dead_bwd<16>, dgrid, dim3(256), 0, s, a);
-    else if (p.dh == 32) hipLaunchKernelGGL(k_attn_dead_bwd<32>, dgrid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_attn_dead_bwd<64>, dgrid, dim3(256), 0, s, a);
+    dim3 dgrid((p.n + 256 / p.dh - 1) / (256 / p.dh), p.b * (gqa ? p.Hkv : p.H));
+    XTRL_ATTN_LAUNCH_DH(k_attn_dead_bwd, gqa, p.dh, dgrid);
     XTRL_LAUNCHED("attn_dead_bwd");
   }
   return XTRL_OK;
@@ -879,21 +967,30 @@ int64_t attn_dq_part_floats(int b, int H, int n, int dh) {
 }
 
 AttnProblem contiguous_problem(const int32_t* lens, int b, int H, int n, int dh, float scale, float p, uint64_t seed,
-                               uint32_t offset, uint32_t sub, int window) {
+                               uint32_t offset, uint32_t sub, int window, int Hkv) {
   AttnProblem pr{b, H, n, dh, lens, scale, p, seed, offset, {}, {}, {}, {}};
   pr.sub = sub;
   pr.window = window;
   pr.in = pr.out = pr.grad = attn_layout_bhnd(H, n, dh);
+  pr.Hkv = Hkv;   // k, v, dk, dv [b][Hkv][n][dh] (checked by fill_args)
+  if (Hkv > 0) pr.kv = pr.kvgrad = attn_layout_bhnd(Hkv, n, dh);
   return pr;
 }
 
 }  // namespace xtrl
 
+extern "C" int xtrl_attn_fwd_gqa(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
+                                 float* lse, int b, int H, int Hkv, int n, int dh, float scale, float dropout_p,
+                                 uint64_t seed, uint32_t offset, uint32_t sub, int window, void* stream) {
+  XTRL_REQUIRE(Hkv >= 1, "attn_fwd_gqa: kv heads %d < 1", Hkv);
+  return xtrl::attn_fwd_ex(xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv),
+                           q, k, v, o, lse, nullptr, nullptr, xtrl::as_stream(stream));
+}
+
 extern "C" int xtrl_attn_fwd_win(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
                                  float* lse, int b, int H, int n, int dh, float scale, float dropout_p, uint64_t seed,
                                  uint32_t offset, uint32_t sub, int window, void* stream) {
-  return xtrl::attn_fwd_ex(xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window), q, k,
-                           v, o, lse, nullptr, nullptr, xtrl::as_stream(stream));
+  return xtrl_attn_fwd_gqa(q, k, v, lens, o, lse, b, H, H, n, dh, scale, dropout_p, seed, offset, sub, window, stream);
 }
 
 extern "C" int xtrl_attn_fwd(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
@@ -906,15 +1003,25 @@ extern "C" int64_t xtrl_attn_bwd_part_floats(int b, int H, int n, int dh) {
   return xtrl::attn_dq_part_floats(b, H, n, dh);
 }
 
+extern "C" int xtrl_attn_bwd_part_gqa(const float* q, const float* k, const float* v, const int32_t* lens,
+                                      const float* o, const float* lse, const float* dout, float* dq, float* dk,
+                                      float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats, int b, int H,
+                                      int Hkv, int n, int dh, float scale, float dropout_p, uint64_t seed,
+                                      uint32_t offset, uint32_t sub, int window, void* stream) {
+  XTRL_REQUIRE(Hkv >= 1, "attn_bwd_part_gqa: kv heads %d < 1", Hkv);
+  xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv);
+  pr.dq_part = dq_part;
+  pr.dq_part_floats = dq_part_floats;
+  return xtrl::attn_bwd_ex(pr, q, k, v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+}
+
 extern "C" int xtrl_attn_bwd_part_win(const float* q, const float* k, const float* v, const int32_t* lens,
                                       const float* o, const float* lse, const float* dout, float* dq, float* dk,
                                       float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats, int b, int H,
                                       int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset,
                                       uint32_t sub, int window, void* stream) {
-  xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window);
-  pr.dq_part = dq_part;
-  pr.dq_part_floats = dq_part_floats;
-  return xtrl::attn_bwd_ex(pr, q, k, v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+  return xtrl_attn_bwd_part_gqa(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, dq_part, dq_part_floats, b, H, H, n,
+                                dh, scale, dropout_p, seed, offset, sub, window, stream);
 }
 
 extern "C" int xtrl_attn_bwd_part(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
@@ -925,12 +1032,21 @@ extern "C" int xtrl_attn_bwd_part(const float* q, const float* k, const float* v
                                 scale, dropout_p, seed, offset, sub, 0, stream);
 }
 
+extern "C" int xtrl_attn_bwd_gqa(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                                 const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                                 int b, int H, int Hkv, int n, int dh, float scale, float dropout_p, uint64_t seed,
+                                 uint32_t offset, uint32_t sub, int window, void* stream) {
+  XTRL_REQUIRE(Hkv >= 1, "attn_bwd_gqa: kv heads %d < 1", Hkv);
+  return xtrl::attn_bwd_ex(xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv),
+                           q, k, v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+}
+
 extern "C" int xtrl_attn_bwd_win(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
                                  const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
                                  int b, int H, int n, int dh, float scale, float dropout_p, uint64_t seed,
                                  uint32_t offset, uint32_t sub, int window, void* stream) {
-  return xtrl::attn_bwd_ex(xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window), q, k,
-                           v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+  return xtrl_attn_bwd_gqa(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, b, H, H, n, dh, scale, dropout_p, seed,
+                           offset, sub, window, stream);
 }
 
 extern "C" int xtrl_attn_bwd(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,

@@ -344,6 +344,11 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
   const int idx = blockIdx.x * nw + w;
   const int H = D.H, I = H * DH, d = D.d;
   const int r = idx / H, h = idx - r * H;
+  // grouped-query attention (D.Hkv < H): this wave's kv head; the group's lowest query head stores the
+  // new K / V (and layer-0 v1) row, the others form the same k, v in registers and read rows < t only
+  const int Hkv = D.Hkv > 0 ? D.Hkv : H, Ikv = Hkv * DH;
+  const int kvh = Hkv == H ? h : kv_head_of(h, Hkv);
+  const bool kv_owner = Hkv == H || kv_head_owner(h, Hkv);
   constexpr bool FUSE = FJ > 0;
   // the live count and the row's slot in one round trip (live_rows past the count: a stale slot)
   const int n_live = D.live_count[t & 1];
@@ -383,26 +388,26 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
   float* vs = ks + DH;
   const float* row = D.qkv + (int64_t)r * D.n_qkv;
   const int c = lane % DH, g = lane / DH;
-  float q = row[h * DH + c], k = row[I + h * DH + c], v = row[2 * I + h * DH + c];
+  float q = row[h * DH + c], k = row[I + kvh * DH + c], v = row[I + Ikv + kvh * DH + c];
   float v1v = 0.f, mixv = 0.f, gate4[4] = {0.f, 0.f, 0.f, 0.f};
   // P.V lane roles: key kk = lane % KPI of a load instruction's KPI rows, channel quad cq = lane / KPI
   // (the KPI rows of one instruction are consecutive: 1 KiB contiguous; the reduction over kk stays
   // inside a 16-lane row: DPP steps, no cross-lane permutes)
   const int kk = lane % KPI, cq = lane / KPI;
   if (D.value_residual && layer > 0) {
-    v1v = D.v1[(int64_t)r * I + h * DH + c];
-    if (D.learned_mix) mixv = row[3 * I + (D.gate_values ? I : 0) + h];
+    v1v = D.v1[(int64_t)r * Ikv + kvh * DH + c];
+    if (D.learned_mix) mixv = row[I + 2 * Ikv + (D.gate_values ? I : 0) + kvh];
   }
   if (D.gate_values) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) gate4[i] = row[3 * I + h * DH + 4 * cq + i];
+    for (int i = 0; i < 4; ++i) gate4[i] = row[I + 2 * Ikv + h * DH + 4 * cq + i];
   }
   // the first chunk of the cache (rows written by earlier steps; rows >= t clamped, masked below).
   // Sliding window (attn_window W > 0): the query at position t sees the keys j_lo = max(0, t - W) .. t
   // only.  The cache pointers and the score slots are moved up by j_lo and the loops below run over
   // the window-relative positions 0 .. tw = t - j_lo (loads clamped to [j_lo, t - 1] absolute) —
   // W < 128: the windowed cache read is this one prefetch.  No window: j_lo = 0, tw = t
-  const int64_t cache_base = ((int64_t)e * H + h) * D.Tmax * DH;
+  const int64_t cache_base = ((int64_t)e * Hkv + kvh) * D.Tmax * DH;
   const int j_lo = D.attn_window > 0 ? max(t - D.attn_window, 0) : 0;
   const int tw = t - j_lo;
   const float* Kc = Ly.k_cache + cache_base + (int64_t)j_lo * DH;
@@ -420,7 +425,7 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
   // value residual (first layer stores its values; later layers lerp toward them)
   if (D.value_residual) {
     if (layer == 0) {
-      if (g == 0) D.v1[(int64_t)r * I + h * DH + c] = v;
+      if (g == 0 && kv_owner) D.v1[(int64_t)r * Ikv + kvh * DH + c] = v;
     } else if (D.learned_mix) {
       v = lerpf_(v, v1v, sigmoidf_(mixv));
     }
@@ -432,8 +437,10 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
     qs[c] = q;
     ks[c] = k;
     vs[c] = v;
-    Ly.k_cache[cache_base + (int64_t)t * DH + c] = k;
-    Ly.v_cache[cache_base + (int64_t)t * DH + c] = v;
+    if (kv_owner) {
+      Ly.k_cache[cache_base + (int64_t)t * DH + c] = k;
+      Ly.v_cache[cache_base + (int64_t)t * DH + c] = v;
+    }
   }
   wave_sync();
   const float scale = D.attn_scale > 0.f ? D.attn_scale : 1.0f / sqrtf((float)DH);
@@ -963,8 +970,11 @@ int check_desc(const XtrlDecodeDesc* D) {
                "decode: bad dims (d must be a multiple of 4, at most 512)");
   XTRL_REQUIRE(D->in_dim == 2 * D->d + (D->evolutionary ? D->d : 0), "decode: in_dim mismatch");
   const int I = D->H * D->dh;
-  XTRL_REQUIRE(D->n_qkv == 3 * I + (D->gate_values ? I : 0) + ((D->value_residual && D->learned_mix) ? D->H : 0),
-               "decode: n_qkv mismatch");
+  XTRL_REQUIRE(D->Hkv >= 0 && D->Hkv <= D->H && D->H % (D->Hkv > 0 ? D->Hkv : D->H) == 0,
+               "decode: Hkv %d must divide H %d (0 = H)", D->Hkv, D->H);
+  const int Hkv = D->Hkv > 0 ? D->Hkv : D->H;
+  XTRL_REQUIRE(D->n_qkv == I + 2 * Hkv * D->dh + (D->gate_values ? I : 0) + ((D->value_residual && D->learned_mix) ? Hkv : 0),
+               "decode: n_qkv mismatch (I + 2 Ikv (+ I gate) (+ Hkv mix))");
   XTRL_REQUIRE(!D->ff_glu || (D->hglu && D->hff), "decode: ff_glu needs hglu");
   XTRL_REQUIRE(D->attn_window >= 0, "decode: attn_window %d < 0 (0 = no window)", D->attn_window);
   return XTRL_OK;
@@ -1807,7 +1817,7 @@ __host__ __device__ inline RowLds row_lds(const XtrlDecodeDesc& D) {
   o.xn = at; at += round4i(D.d);
   o.qkv = at; at += nq;
   o.att = at; at += round4i(I);
-  o.v1 = at; at += round4i(I);
+  o.v1 = at; at += round4i((D.Hkv > 0 ? D.Hkv : D.H) * D.dh);   // the first layer's values, per kv head
   o.h = at; at += round4i(hw);
   o.ac = at; at += round4i(D.in_dim);
   o.part = at; at += ROW_PART + n2;   // partial rows (+ the heads' output row behind them)
@@ -1901,6 +1911,7 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
   };
   mark();
   const int S = D.S, d = D.d, H = D.H, I = H * DH, L = D.L;
+  const int Hkv = D.Hkv > 0 ? D.Hkv : H, Ikv = Hkv * DH;   // kv heads (grouped-query attention; = H without)
   // the layer descriptors (pointers) copied to LDS in one batch of vector loads: read lazily from
   // layers_dev, each layer phase's pointers were a cold scalar load ahead of its data (a round trip per phase)
   __shared__ XtrlDecodeLayer ly_sh[ROW_MAX_L];
@@ -2020,22 +2031,26 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
       for (int h = w; h < H; h += ROW_T / 64) {
         const int c = lane % DH, g = lane / DH;
         float* sc = lds + Lo.sc + h * (round4i(D.Tmax) + 64);
-        float q = qkv[h * DH + c], k = qkv[I + h * DH + c], v = qkv[2 * I + h * DH + c];
+        // grouped-query attention, as k_attn_decode: kv head kvh; the group's lowest query head stores
+        // the kv head's new rows (v1s / v1 / the caches), the others form the same k, v in registers
+        const int kvh = Hkv == H ? h : kv_head_of(h, Hkv);
+        const bool kv_owner = Hkv == H || kv_head_owner(h, Hkv);
+        float q = qkv[h * DH + c], k = qkv[I + kvh * DH + c], v = qkv[I + Ikv + kvh * DH + c];
         if (D.value_residual) {
           if (l == 0) {
-            if (g == 0) {
-              v1s[h * DH + c] = v;
-              if (lead) D.v1[(int64_t)r * I + h * DH + c] = v;
+            if (g == 0 && kv_owner) {
+              v1s[kvh * DH + c] = v;
+              if (lead) D.v1[(int64_t)r * Ikv + kvh * DH + c] = v;
             }
           } else if (D.learned_mix) {
-            v = lerpf_(v, v1s[h * DH + c], sigmoidf_(qkv[3 * I + (D.gate_values ? I : 0) + h]));
+            v = lerpf_(v, v1s[kvh * DH + c], sigmoidf_(qkv[I + 2 * Ikv + (D.gate_values ? I : 0) + kvh]));
           }
         }
         if (D.qk_norm) qk_l2norm<DH>(q, k);
         if (D.rotary_abs && c < D.rot_dim) rotary_row(D, t, c, q, k);
-        const int64_t cb = ((int64_t)e * H + h) * D.Tmax * DH;
+        const int64_t cb = ((int64_t)e * Hkv + kvh) * D.Tmax * DH;
         if (g == 0) {
-          if (lead) {
+          if (lead && kv_owner) {
             Ly.k_cache[cb + (int64_t)t * DH + c] = k;
             Ly.v_cache[cb + (int64_t)t * DH + c] = v;
           }
@@ -2132,7 +2147,7 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
                          (acc.w + pn * vn[3]) / sum};
           if (D.gate_values) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) o4[i] *= sigmoidf_(qkv[3 * I + h * DH + 4 * cq + i]);
+            for (int i = 0; i < 4; ++i) o4[i] *= sigmoidf_(qkv[I + 2 * Ikv + h * DH + 4 * cq + i]);
           }
           *reinterpret_cast<float4*>(att + h * DH + 4 * cq) = make_float4(o4[0], o4[1], o4[2], o4[3]);
         }

@@ -213,7 +213,23 @@ struct AttnProblem {
   // sliding window (x-transformers max_attend_past): key j visible to query i only if i - j <= window,
   // on top of the causal and key-padding masks; 0: no window
   int window = 0;
+  // grouped-query attention (x-transformers attn_kv_heads): k, v, dk, dv hold Hkv heads (H % Hkv == 0),
+  // query head h reads kv head kv_head_of(h, Hkv); dk / dv are the sums over a kv head's query heads.
+  // 0 or H: one kv head per query head (k, v in `in`, dk, dv in `grad`).  Hkv < H: k, v are addressed
+  // with `kv` and dk, dv with `kvgrad` (q and dq keep `in` and `grad`)
+  int Hkv = 0;
+  AttnLayout kv = {}, kvgrad = {};
 };
+// the kv head that query head h reads: x-transformers repeats k / v as 'b kvh n d -> b (r kvh) n d', so
+// the repeated head r * Hkv + kvh is kv head kvh.  The one place on the device side that knows the mapping
+__host__ __device__ inline int kv_head_of(int h, int Hkv) { return h % Hkv; }
+// whether h is the lowest query head of its kv head: in the cached decode (a wave per query head) that
+// wave stores the kv head's new K / V row; the others of the group form the same row in registers
+__host__ __device__ inline bool kv_head_owner(int h, int Hkv) {
+  for (int x = 0; x < h; ++x)
+    if (kv_head_of(x, Hkv) == kv_head_of(h, Hkv)) return false;
+  return true;
+}
 int64_t attn_dq_part_floats(int b, int H, int n, int dh);
 
 // o (ungated) and lse; if gate != nullptr also og = o * sigmoid(gate) (og in the `out` layout)

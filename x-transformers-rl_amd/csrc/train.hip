@@ -349,16 +349,25 @@ __global__ __launch_bounds__(64 * LN_WAVES) void k_ln_bwd(const float* g1, int l
 // one thread per (token, column pair) of q | k | v (coalesced float2 traffic): q and k rotated on
 // their first rot_dim channels (interleaved pairs, position = step within the episode); v mixed
 // towards the first layer's v
+// Grouped-query attention: the q segment is I = H dh columns, the k and v segments Ikv = Hkv dh each
+// (Ikv = I without it); the mix is one column per kv head and the first layer's values are Ikv wide
 struct PrepArgs {
   const float* proj;    // [T][n_qkv]
-  const float* vfirst;  // layer-0 proj (v at column 2I)
-  float* qkv;           // [T][3I]
+  const float* vfirst;  // layer-0 proj (v at column I + Ikv)
+  float* qkv;           // [T][I + 2 Ikv]
   const float* inv_freq;
   int T, n, H, dh, I, n_qkv, ld_vfirst, rot_dim, mix_col;   // mix_col < 0: no mix
   int qk_norm;          // x-transformers qk norm: q, k l2-normalised per head before the rotary
   float xpos_base;      // rotary xPos scale base (0: off)
   const int32_t* rows;  // packed rows (grid (pair blocks, T)): token t's position is rows[t] % n
+  int Ikv;              // width of the k and of the v segment (Hkv dh)
 };
+
+// segment (0 q, 1 k, 2 v) and column within it of column col of a q [I] | k [Ikv] | v [Ikv] row
+__device__ __forceinline__ void qkv_segment(int col, int I, int Ikv, int& seg, int& within) {
+  seg = col < I ? 0 : (col < I + Ikv ? 1 : 2);
+  within = col - (seg == 0 ? 0 : (seg == 1 ? I : I + Ikv));
+}
 
 // x-transformers RotaryEmbedding(use_xpos): rotated pair j (even channel) at position pos of an n-token
 // sequence is scaled by ((j + 0.4 rot) / (1.4 rot)) ^ ((pos - n / 2) / scale_base) for q, by its
@@ -380,12 +389,14 @@ __device__ __forceinline__ float head_norm(float2 x, int dh) {
 // (no 64-bit division per element); one sincosf per rotated pair
 constexpr int PREP_T = 128;
 __global__ __launch_bounds__(PREP_T) void k_qkv_prep(const PrepArgs a) {
-  const int P = 3 * a.I / 2;
+  const int P = (a.I + 2 * a.Ikv) / 2;
   const int pair = blockIdx.x * PREP_T + threadIdx.x;
   if (pair >= P) return;
   const int t = a.rows ? (int)blockIdx.y : blockIdx.z * a.n + blockIdx.y;
   const int pos = a.rows ? a.rows[t] % a.n : (int)blockIdx.y, col = 2 * pair;
-  const int seg = col / a.I, within = col - seg * a.I, h = within / a.dh, j = within - h * a.dh;
+  int seg, within;
+  qkv_segment(col, a.I, a.Ikv, seg, within);
+  const int h = within / a.dh, j = within - h * a.dh;   // (k, v: the kv head)
   float2 x = *reinterpret_cast<const float2*>(a.proj + (int64_t)t * a.n_qkv + col);
   float2 y;
   if (seg < 2) {
@@ -411,13 +422,13 @@ __global__ __launch_bounds__(PREP_T) void k_qkv_prep(const PrepArgs a) {
     }
   } else if (a.mix_col >= 0) {
     const float m = sigmoidf_(a.proj[(int64_t)t * a.n_qkv + a.mix_col + h]);
-    const float2 vf = *reinterpret_cast<const float2*>(a.vfirst + (int64_t)t * a.ld_vfirst + 2 * a.I + within);
+    const float2 vf = *reinterpret_cast<const float2*>(a.vfirst + (int64_t)t * a.ld_vfirst + a.I + a.Ikv + within);
     y.x = lerpf_(x.x, vf.x, m);
     y.y = lerpf_(x.y, vf.y, m);
   } else {
     y = x;
   }
-  *reinterpret_cast<float2*>(a.qkv + (int64_t)t * 3 * a.I + col) = y;
+  *reinterpret_cast<float2*>(a.qkv + (int64_t)t * (a.I + 2 * a.Ikv) + col) = y;
 }
 
 // backward of k_qkv_prep, in place on dproj ([T][n_qkv], dq | dk | dv written by the attention
@@ -428,22 +439,25 @@ struct PrepBwdArgs {
   float* dproj;
   const float* proj;
   const float* vfirst;
-  float* dvfirst;       // [T][I]
+  float* dvfirst;       // [T][Ikv]
   const float* inv_freq;
   int T, n, H, dh, I, n_qkv, ld_vfirst, rot_dim, mix_col, first_layer, accumulate;
   int qk_norm;
   float xpos_base;
   const int32_t* rows;  // packed rows, as PrepArgs
+  int Ikv;              // as PrepArgs
 };
 
 __global__ __launch_bounds__(PREP_T) void k_qkv_prep_bwd(const PrepBwdArgs a) {
-  const int P = 3 * a.I / 2;
+  const int P = (a.I + 2 * a.Ikv) / 2;
   const int pair0 = blockIdx.x * PREP_T + threadIdx.x;
   const bool valid = pair0 < P;
   const int pair = valid ? pair0 : 0;
   const int t = a.rows ? (int)blockIdx.y : blockIdx.z * a.n + blockIdx.y;
   const int pos = a.rows ? a.rows[t] % a.n : (int)blockIdx.y, col = 2 * pair;
-  const int seg = col / a.I, within = col - seg * a.I, h = within / a.dh, j = within - h * a.dh;
+  int seg, within;
+  qkv_segment(col, a.I, a.Ikv, seg, within);
+  const int h = within / a.dh, j = within - h * a.dh;   // (k, v: the kv head)
   float* g = a.dproj + (int64_t)t * a.n_qkv + col;
   float dm = 0.f, m = 0.f;
   float2 gqk = make_float2(0.f, 0.f);   // q / k: the gradient w.r.t. the (normalised) pre-rotary pair
@@ -467,7 +481,7 @@ __global__ __launch_bounds__(PREP_T) void k_qkv_prep_bwd(const PrepBwdArgs a) {
       }
       gqk = gv;
     } else {
-      float2* dvf = reinterpret_cast<float2*>(a.dvfirst + (int64_t)t * a.I + within);
+      float2* dvf = reinterpret_cast<float2*>(a.dvfirst + (int64_t)t * a.Ikv + within);
       if (a.mix_col >= 0) {
         const float* pr = a.proj + (int64_t)t * a.n_qkv;
         m = sigmoidf_(pr[a.mix_col + h]);
@@ -1126,6 +1140,11 @@ int dgrad_ln_bwd(const Ctx& c, const float* dY, int ldy, const float* W, int N, 
   return XTRL_OK;
 }
 
+// grouped-query attention (XtrlTrainDesc.Hkv, 0 = H): the kv head count and the width of the k and v
+// segments.  A projection row is q [I] | k [Ikv] | v [Ikv] | gate [I] | mix [Hkv]
+inline int kv_heads(const XtrlTrainDesc* D) { return D->Hkv > 0 ? D->Hkv : D->H; }
+inline int kv_inner(const XtrlTrainDesc* D) { return kv_heads(D) * D->dh; }
+
 AttnProblem attn_problem(const Ctx& c, const XtrlTrainLayer& Ly, int li) {
   const XtrlTrainDesc* D = c.D;
   const int I = D->H * D->dh;
@@ -1140,7 +1159,7 @@ AttnProblem attn_problem(const Ctx& c, const XtrlTrainLayer& Ly, int li) {
   p.seed = D->seed;
   p.offset = D->attn_offset;
   p.sub = (uint32_t)li;
-  p.in = attn_layout_tokens(D->n, 3 * I, D->dh);
+  p.in = attn_layout_tokens(D->n, I + 2 * kv_inner(D), D->dh);
   p.out = attn_layout_tokens(D->n, I, D->dh);
   p.grad = attn_layout_tokens(D->n, Ly.n_qkv, D->dh);
   p.gate = attn_layout_tokens(D->n, Ly.n_qkv, D->dh);
@@ -1148,6 +1167,10 @@ AttnProblem attn_problem(const Ctx& c, const XtrlTrainLayer& Ly, int li) {
   p.dq_part = D->dq_part;
   p.dq_part_floats = D->dq_part_floats;
   p.window = D->attn_window;
+  // grouped-query attention: k, v (and dk, dv) are token rows of the same buffers as q (dq), Hkv heads wide
+  p.Hkv = kv_heads(D);
+  p.kv = p.in;
+  p.kvgrad = p.grad;
   return p;
 }
 
@@ -1156,6 +1179,12 @@ int validate(const XtrlTrainDesc* D) {
   XTRL_REQUIRE(D->b > 0 && D->n > 0 && D->d > 0 && D->L > 0 && D->H > 0 && D->dh > 0, "train: bad sizes");
   XTRL_REQUIRE(D->d <= 64 * kMaxDPerLane, "train: d = %d > %d unsupported", D->d, 64 * kMaxDPerLane);
   XTRL_REQUIRE(D->dh % 2 == 0 && D->rot_dim <= D->dh, "train: bad rotary dims");
+  XTRL_REQUIRE(D->Hkv >= 0 && D->Hkv <= D->H && D->H % kv_heads(D) == 0, "train: Hkv %d must divide H %d (0 = H)", D->Hkv,
+               D->H);
+  for (int li = 0; li < D->L; ++li)
+    XTRL_REQUIRE(D->layers[li].n_qkv == D->H * D->dh + 2 * kv_inner(D) + (D->gate_values ? D->H * D->dh : 0) +
+                                            (D->layers[li].mix ? kv_heads(D) : 0),
+                 "train: layer %d n_qkv %d is not I + 2 Ikv (+ I gate) (+ Hkv mix)", li, D->layers[li].n_qkv);
   XTRL_REQUIRE(D->in_dim == D->d * (D->evolutionary ? 3 : 2), "train: in_dim mismatch");
   XTRL_REQUIRE(D->ld_ff == 0 || (D->ld_ff >= D->ff && D->ld_ff % 4 == 0), "train: ld_ff %d (ff %d)", D->ld_ff, D->ff);
   XTRL_REQUIRE(!D->ff_glu || (D->ld_u2 >= 2 * D->ff && D->ld_u2 % 4 == 0 && D->glu_dh),
@@ -1373,6 +1402,7 @@ int train_forward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
   const Ctx c{D, s, Trows};
   const int32_t* rows = D->packed ? D->vrows : nullptr;
   const int T = c.T, d = D->d, I = D->H * D->dh, ff = D->ff, lf = ld_ff(D);
+  const int Ikv = kv_inner(D), nq3 = I + 2 * Ikv;   // the k / v segment width; q | k | v columns of a projection row
   int rc;
   // embeddings
   if (D->evolutionary) {
@@ -1405,17 +1435,17 @@ int train_forward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     if (!fuse)
       if ((rc = ln_fwd(c, Ly.x_attn, c.P(Ly.ln_attn), Ly.xn_attn, d, nullptr, 0, Ly.st_attn))) return rc;
     if ((rc = linear_fwd(c, Ly.xn_attn, d, c.P(Ly.w_proj), c.P(Ly.b_proj), Ly.proj, Ly.n_qkv, T, Ly.n_qkv, d,
-                         EPI_NONE, nullptr, nullptr, 0, 1 << 30, 3 * I)))
+                         EPI_NONE, nullptr, nullptr, 0, 1 << 30, nq3)))
       return rc;
-    const int mix_col = Ly.mix ? 3 * I + (D->gate_values ? I : 0) : -1;
+    const int mix_col = Ly.mix ? nq3 + (D->gate_values ? I : 0) : -1;
     PrepArgs pa{Ly.proj, D->layers[0].proj, Ly.qkv, D->inv_freq, T, D->n, D->H, D->dh, I, Ly.n_qkv,
-                D->layers[0].n_qkv, D->rot_dim, mix_col, D->qk_norm, D->xpos_base, rows};
-    const dim3 pg = rows ? dim3(blocks(3 * I / 2, PREP_T), T) : dim3(blocks(3 * I / 2, PREP_T), D->n, D->b);
+                D->layers[0].n_qkv, D->rot_dim, mix_col, D->qk_norm, D->xpos_base, rows, Ikv};
+    const dim3 pg = rows ? dim3(blocks(nq3 / 2, PREP_T), T) : dim3(blocks(nq3 / 2, PREP_T), D->n, D->b);
     hipLaunchKernelGGL(k_qkv_prep, pg, dim3(PREP_T), 0, s, pa);
     XTRL_LAUNCHED("train qkv_prep");
     const AttnProblem ap = attn_problem(c, Ly, li);
-    if ((rc = attn_fwd_ex(ap, Ly.qkv, Ly.qkv + I, Ly.qkv + 2 * I, Ly.o, Ly.lse,
-                          D->gate_values ? Ly.proj + 3 * I : nullptr, D->gate_values ? Ly.og : nullptr, s)))
+    if ((rc = attn_fwd_ex(ap, Ly.qkv, Ly.qkv + I, Ly.qkv + I + Ikv, Ly.o, Ly.lse,
+                          D->gate_values ? Ly.proj + nq3 : nullptr, D->gate_values ? Ly.og : nullptr, s)))
       return rc;
     if (fuse) {
       if ((rc = linear_res_ln(c, D->gate_values ? Ly.og : Ly.o, I, c.P(Ly.w_out), nullptr, Ly.x_attn, Ly.x_ff, I,
@@ -1465,6 +1495,7 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
   const Ctx c{D, s, Trows};
   const int32_t* rows = D->packed ? D->vrows : nullptr;
   const int T = c.T, d = D->d, I = D->H * D->dh, ff = D->ff, lf = ld_ff(D);
+  const int Ikv = kv_inner(D), nq3 = I + 2 * Ikv;   // the k / v segment width; q | k | v columns of a projection row
   int rc;
   SideStream& side = side_stream();
   const bool two = side.ok && side.ensure(side_events_needed(D->L));
@@ -1598,16 +1629,16 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     if ((rc = wait(e_proj))) return rc;
     if (D->gate_values) {
       if ((rc = linear_dgrad(c, xg, d, c.P(Ly.w_out), D->dog, I, T, d, I, EPI_DGATE, Ly.o, I, 1 << 30,
-                             Ly.proj + 3 * I, Ly.n_qkv, dproj + 3 * I, Ly.n_qkv)))
+                             Ly.proj + nq3, Ly.n_qkv, dproj + nq3, Ly.n_qkv)))
         return rc;
     } else {
       if ((rc = linear_dgrad(c, xg, d, c.P(Ly.w_out), D->dog, I, T, d, I, EPI_NONE))) return rc;
     }
     const AttnProblem ap = attn_problem(c, Ly, li);
-    if ((rc = attn_bwd_ex(ap, Ly.qkv, Ly.qkv + I, Ly.qkv + 2 * I, Ly.o, Ly.lse, D->dog, dproj, dproj + I,
-                          dproj + 2 * I, D->delta, s)))
+    if ((rc = attn_bwd_ex(ap, Ly.qkv, Ly.qkv + I, Ly.qkv + I + Ikv, Ly.o, Ly.lse, D->dog, dproj, dproj + I,
+                          dproj + I + Ikv, D->delta, s)))
       return rc;
-    const int mix_col = Ly.mix ? 3 * I + (D->gate_values ? I : 0) : -1;
+    const int mix_col = Ly.mix ? nq3 + (D->gate_values ? I : 0) : -1;
     const bool any_mix = [&] {
       for (int j = 1; j < D->L; ++j)
         if (D->layers[j].mix) return true;
@@ -1618,13 +1649,13 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     for (int j = li + 1; j < D->L; ++j) deeper_mix = deeper_mix || D->layers[j].mix;
     PrepBwdArgs pb{dproj, Ly.proj, D->layers[0].proj, D->dvfirst, D->inv_freq, T, D->n, D->H, D->dh, I,
                    Ly.n_qkv, D->layers[0].n_qkv, D->rot_dim, mix_col, li == 0 ? 1 : 0,
-                   (li == 0 ? any_mix : deeper_mix) ? 1 : 0, D->qk_norm, D->xpos_base, rows};
-    const dim3 pg = rows ? dim3(blocks(3 * I / 2, PREP_T), T) : dim3(blocks(3 * I / 2, PREP_T), D->n, D->b);
+                   (li == 0 ? any_mix : deeper_mix) ? 1 : 0, D->qk_norm, D->xpos_base, rows, Ikv};
+    const dim3 pg = rows ? dim3(blocks(nq3 / 2, PREP_T), T) : dim3(blocks(nq3 / 2, PREP_T), D->n, D->b);
     hipLaunchKernelGGL(k_qkv_prep_bwd, pg, dim3(PREP_T), 0, s, pb);
     XTRL_LAUNCHED("train qkv_prep_bwd");
     // q | k | v | gate | mix projection
     if ((rc = F.fork())) return rc;
-    if ((rc = wgrad(cw, dproj, Ly.n_qkv, Ly.xn_attn, d, c.G(Ly.w_proj), T, Ly.n_qkv, d, c.G(Ly.b_proj), 3 * I)))
+    if ((rc = wgrad(cw, dproj, Ly.n_qkv, Ly.xn_attn, d, c.G(Ly.w_proj), T, Ly.n_qkv, d, c.G(Ly.b_proj), nq3)))
       return rc;
     e_proj = F.mark();
     if (fuse) {

@@ -107,7 +107,7 @@ class Agent(nn.Module):
                  # extensions (decision log in DESIGN.md)
                  reward_dropout=0.5, seed=0, rotary_abs_rollout=False, hl_reduction_mean=True, hl_sigma_ratio=2.0,
                  fused_learn=True, device=None, truncation_bootstrap=True, policy_body='decoder', fractal_levels=None,
-                 packed_learn=False):
+                 packed_learn=False, kv_heads=None):
         super().__init__()
         self.accelerator = accelerator if accelerator is not None else dist_.DistContext(device)
         dev = self.accelerator.device
@@ -127,16 +127,35 @@ class Agent(nn.Module):
         known = {'attn_dim_head', 'heads', 'depth', 'attn_gate_values', 'add_value_residual',
                  'learned_value_residual_mix', 'ff_mult', 'ff_no_bias', 'ff_glu', 'attn_qk_norm',
                  'attn_qk_norm_scale', 'rotary_xpos', 'rotary_xpos_scale_base', 'use_rmsnorm',
-                 'attn_max_attend_past'}
+                 'attn_max_attend_past', 'attn_one_kv_head'}
         unknown = set(wm) - known
         if unknown:
+            # (world_model['attn_kv_heads'] stays among the refused options, as before grouped-query attention
+            # existed: the kv head count is the Agent's own ``kv_heads`` argument, or attn_one_kv_head for one)
+            hint = (' — grouped-query attention is selected with agent_kwargs=dict(kv_heads=Hkv), or '
+                    "world_model['attn_one_kv_head']=True for one kv head" if 'attn_kv_heads' in unknown else '')
             raise NotImplementedError(f'world_model options {sorted(unknown)} are not supported by the MI355X decoder '
                                       f'(supported: {sorted(known)}, implementation switches attn_flash / '
-                                      f'attn_onnxable, and any option at its x-transformers default)')
+                                      f'attn_onnxable, and any option at its x-transformers default){hint}')
         # sliding window (x-transformers Attention max_attend_past): query i sees key j iff 0 <= i - j <= W
         window = wm.get('attn_max_attend_past')
         if window is not None and (isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1):
             raise ValueError(f'attn_max_attend_past must be an int >= 1 or None (no window), not {window!r}')
+        # grouped-query attention (x-transformers Attention kv_heads / one_kv_head): to_k, to_v and the
+        # value-residual mix have Hkv heads, query head h reads kv head h % Hkv (ops.kv_head_index)
+        # The head count comes from the ``kv_heads`` argument (x-transformers' attn_kv_heads restated), or from
+        # world_model['attn_one_kv_head'] = True (one kv head)
+        heads = wm.get('heads', 8)
+        if wm.get('attn_one_kv_head', False):
+            if kv_heads is not None:
+                raise ValueError('kv_heads and attn_one_kv_head cannot both be given (attn_one_kv_head means '
+                                 'kv_heads=1)')
+            kv_heads = 1
+        if kv_heads is not None and (isinstance(kv_heads, bool) or not isinstance(kv_heads, (int, np.integer))
+                                     or not 1 <= kv_heads <= heads or heads % kv_heads):
+            raise ValueError(f'kv_heads must be an int from 1 to heads = {heads} that divides heads, or None, '
+                             f'not {kv_heads!r}')
+        kv_heads = 0 if kv_heads is None or kv_heads == heads else int(kv_heads)   # 0: plain multi-head attention
         self.seed = int(seed)
         self.evolutionary = evolutionary
         self.evolve_every, self.evolve_after_step = evolve_every, evolve_after_step
@@ -154,7 +173,7 @@ class Agent(nn.Module):
                         qk_norm_scale=float(wm.get('attn_qk_norm_scale', 10.)),
                         rotary_xpos=bool(wm.get('rotary_xpos', False)),
                         xpos_scale_base=float(wm.get('rotary_xpos_scale_base', 512.)),
-                        rotary_abs_rollout=rotary_abs_rollout, attn_window=int(window or 0),
+                        rotary_abs_rollout=rotary_abs_rollout, attn_window=int(window or 0), kv_heads=kv_heads,
                         hl_reduction_mean=hl_reduction_mean, hl_sigma_ratio=hl_sigma_ratio)
         self.cfg = c
         # the learn step without the minibatch's padding (XtrlTrainDesc.packed): exact only with the
@@ -169,6 +188,9 @@ class Agent(nn.Module):
             if c.attn_window:
                 raise NotImplementedError('the fractal policy body has no sliding window: set attn_max_attend_past '
                                           'to None')
+            if c.kv_heads:
+                raise NotImplementedError('the fractal policy body has no grouped-query attention: leave kv_heads / '
+                                          'attn_one_kv_head unset (or kv_heads = heads)')
             if c.gate_values or c.value_residual or c.ff_no_bias or c.ff_glu or c.qk_norm or c.rotary_xpos or c.rms_norm:
                 raise NotImplementedError('the fractal policy body has no gated values / value residual / bias-free or '
                                           'GLU feed-forward / qk norm / xPos rotary / RMSNorm: set attn_gate_values / '

@@ -53,6 +53,7 @@ class ModelConfig:
     rotary_xpos: bool = False            # x-transformers rotary_xpos: xPos-scaled rotary (q x s^p, k / s^p)
     xpos_scale_base: float = 512.        # x-transformers rotary_xpos_scale_base
     attn_window: int = 0                 # x-transformers attn_max_attend_past: key j visible iff 0 <= i - j <= W (0: none)
+    kv_heads: int = 0                    # kv heads (GQA: Agent kv_heads / attn_one_kv_head); 0 or heads: multi-head
     rotary_abs_rollout: bool = False     # decision log: reference semantics = rotary position 0 in rollout
     hl_reduction_mean: bool = True       # decision log: hl-gauss-pytorch default reduction
     hl_sigma_ratio: float = 2.0
@@ -60,6 +61,16 @@ class ModelConfig:
     @property
     def inner(self):
         return self.heads * self.dim_head
+
+    @property
+    def n_kv_heads(self):
+        """The kv head count: kv_heads, or heads when it is 0 (plain multi-head attention)."""
+        return self.kv_heads or self.heads
+
+    @property
+    def kv_inner(self):
+        """Width of to_k / to_v (and of the k and v segments of a projection row)."""
+        return self.n_kv_heads * self.dim_head
 
     @property
     def in_dim(self):
@@ -98,8 +109,8 @@ class XAttention(nn.Module):
         super().__init__()
         d, inner = c.dim, c.inner
         self.to_q = nn.Linear(d, inner, bias=False)
-        self.to_k = nn.Linear(d, inner, bias=False)
-        self.to_v = nn.Linear(d, inner, bias=False)
+        self.to_k = nn.Linear(d, c.kv_inner, bias=False)   # (grouped-query attention: kv_heads heads)
+        self.to_v = nn.Linear(d, c.kv_inner, bias=False)
         self.to_out = nn.Linear(inner, d, bias=False)
         self.to_v_gate = None
         if c.gate_values:
@@ -108,7 +119,7 @@ class XAttention(nn.Module):
             nn.init.constant_(self.to_v_gate.bias, 10.)
         self.to_value_residual_mix = None
         if mix:
-            self.to_value_residual_mix = nn.Sequential(nn.Linear(d, c.heads))
+            self.to_value_residual_mix = nn.Sequential(nn.Linear(d, c.n_kv_heads))   # one mix per kv head
             nn.init.zeros_(self.to_value_residual_mix[0].weight)
             nn.init.zeros_(self.to_value_residual_mix[0].bias)
 
@@ -294,7 +305,7 @@ class WorldModelActorCritic(nn.Module):
             wn += [pre + 'to_v_gate.weight'] if c.gate_values else []
             wn += [pre + 'to_value_residual_mix.0.weight'] if mix else []
             bn = ([pre + 'to_v_gate.bias'] if c.gate_values else []) + ([pre + 'to_value_residual_mix.0.bias'] if mix else [])
-            n_out = 3 * I + (I if c.gate_values else 0) + (c.heads if mix else 0)
+            n_out = I + 2 * c.kv_inner + (I if c.gate_values else 0) + (c.n_kv_heads if mix else 0)
             entry = dict(w=flat.span(wn).view(n_out, d), wg=flat.span(wn, flat.grad).view(n_out, d), mix=mix,
                          b=flat.span(bn) if bn else None, bg=flat.span(bn, flat.grad) if bn else None)
             self._proj.append(entry)
@@ -332,7 +343,9 @@ class WorldModelActorCritic(nn.Module):
         scale = c.qk_norm_scale if c.qk_norm else dh ** -0.5
         p_drop = c.dropout if self.training else 0.
         first_v = None
-        split = lambda t: t.reshape(b, n, H, dh).permute(0, 2, 1, 3)
+        Hkv, Ikv = c.n_kv_heads, c.kv_inner
+        nq3 = I + 2 * Ikv   # the q | k | v columns of a projection row
+        split = lambda t, heads: t.reshape(b, n, heads, dh).permute(0, 2, 1, 3)
         for li, (attn_l, ff_l) in enumerate(self.blocks()):
             (ln_a, _, _), blk, _ = attn_l
             xn = ln_a(x)
@@ -340,13 +353,14 @@ class WorldModelActorCritic(nn.Module):
             # one projection for q | k | v | gate | mix: one well-shaped GEMM, gradient into the flat buffer
             bias = None
             if P['b'] is not None:
-                bias = torch.cat((self._zero_bias(3 * I, x), P['b']))
-            proj = ops.xlinear(xn, P['w'], bias, P['wg'], P['bg'], self._ws, bg_off=3 * I)
-            q, k, v = split(proj[..., :I]), split(proj[..., I:2 * I]), split(proj[..., 2 * I:3 * I])
-            gate_pre = proj[..., 3 * I:4 * I] if c.gate_values else None
+                bias = torch.cat((self._zero_bias(nq3, x), P['b']))
+            proj = ops.xlinear(xn, P['w'], bias, P['wg'], P['bg'], self._ws, bg_off=nq3)
+            # (k, v and the mix have kv heads; ops.attention maps query head h to kv head kv_head_index[h])
+            q, k, v = split(proj[..., :I], H), split(proj[..., I:I + Ikv], Hkv), split(proj[..., I + Ikv:nq3], Hkv)
+            gate_pre = proj[..., nq3:nq3 + I] if c.gate_values else None
             orig_v = v
             if P['mix'] and first_v is not None:
-                mix = torch.sigmoid(proj[..., -H:]).permute(0, 2, 1)[..., None]
+                mix = torch.sigmoid(proj[..., -Hkv:]).permute(0, 2, 1)[..., None]
                 v = v.lerp(first_v, mix)
             if first_v is None:
                 first_v = orig_v

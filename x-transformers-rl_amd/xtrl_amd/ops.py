@@ -208,20 +208,32 @@ def layernorm(x, gamma, out=None):
 # --------------------------------------------------------------------------------------------
 
 
+def kv_head_index(heads, kv_heads, device=None):
+    """[heads] int64: the kv head that query head h reads under grouped-query attention.  x-transformers
+    repeats k / v as 'b kvh n d -> b (r kvh) n d', so the repeated head r * kv_heads + kvh is kv head kvh:
+    h % kv_heads.  The one Python-side statement of the mapping (the device side: kv_head_of, kernels.h);
+    ``k[:, kv_head_index(H, Hkv)]`` is k repeated to H heads."""
+    return torch.arange(heads, device=device) % kv_heads
+
+
 class AttentionFn(torch.autograd.Function):
-    """softmax(q k^T * scale + causal/key-padding mask) with post-softmax dropout, times v."""
+    """softmax(q k^T * scale + causal/key-padding mask) with post-softmax dropout, times v.  q is
+    [b][H][n][dh]; k, v are [b][Hkv][n][dh] with Hkv dividing H (grouped-query attention: query head h
+    reads kv head kv_head_index(H, Hkv)[h]; dk, dv come back [b][Hkv][n][dh], summed over each group)."""
 
     @staticmethod
     def forward(ctx, q, k, v, lens, scale, dropout_p, seed, offset, sub, window=0):
         lib = L.lib()
         b, H, n, dh = q.shape
-        for t in (q, k, v):
+        Hkv = k.shape[1]
+        assert 1 <= Hkv <= H and H % Hkv == 0, f'kv heads {Hkv} must divide heads {H}'
+        for t, heads in ((q, H), (k, Hkv), (v, Hkv)):
             _f32c(t)
-            assert t.shape == (b, H, n, dh)
+            assert t.shape == (b, heads, n, dh)
         assert lens.dtype == torch.int32 and lens.shape == (b,)
         o = torch.empty_like(q)
         lse = torch.empty(b, H, n, device=q.device, dtype=torch.float32)
-        L.check(lib.xtrl_attn_fwd_win(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), b, H, n, dh,
+        L.check(lib.xtrl_attn_fwd_gqa(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), b, H, Hkv, n, dh,
                                       float(scale), float(dropout_p), int(seed), int(offset), int(sub), int(window),
                                       L.stream()), 'attn_fwd')
         ctx.save_for_backward(q, k, v, lens, o, lse)
@@ -237,15 +249,16 @@ class AttentionFn(torch.autograd.Function):
         do = do.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         delta = torch.empty(b, H, n, device=q.device, dtype=torch.float32)
-        L.check(lib.xtrl_attn_bwd_win(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do),
-                                      L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(delta), b, H, n, dh, scale, p, seed,
-                                      offset, sub, window, L.stream()), 'attn_bwd')
+        L.check(lib.xtrl_attn_bwd_gqa(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do),
+                                      L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(delta), b, H, k.shape[1], n, dh, scale, p,
+                                      seed, offset, sub, window, L.stream()), 'attn_bwd')
         return dq, dk, dv, None, None, None, None, None, None, None
 
 
 def attention(q, k, v, lens, scale, dropout_p=0., seed=0, offset=0, sub=0, window=0):
     """``offset`` / ``sub``: the dropout stream (Philox c2 base and c3 sub-index = decoder layer);
-    ``window`` > 0: query i sees key j only if i - j <= window (x-transformers max_attend_past)."""
+    ``window`` > 0: query i sees key j only if i - j <= window (x-transformers max_attend_past).
+    k, v with fewer heads than q (a divisor): grouped-query attention (x-transformers attn_kv_heads)."""
     return AttentionFn.apply(q.contiguous(), k.contiguous(), v.contiguous(), lens, scale, dropout_p, seed, offset,
                              sub, window)
 

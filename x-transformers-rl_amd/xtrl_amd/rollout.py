@@ -3,7 +3,7 @@
 One ``RolloutEngine`` owns, for a fixed (E envs x Tmax steps) shape:
   * packed decode weights (refreshed from the EMA model once per learning update — the rollout
     policy is constant for the whole update, xtrl.py:1194),
-  * per-layer KV caches [E][H][Tmax][dh], env state, trajectory buffers [E][Tmax][.],
+  * per-layer KV caches [E][Hkv][Tmax][dh] (Hkv = kv heads: grouped-query attention; = H without), env state, trajectory buffers [E][Tmax][.],
   * the ctypes ``XtrlDecodeDesc`` pointing at all of them.
 ``run()`` drives ``xtrl_decode_step`` for t = 0..Tmax-1, either eagerly or by replaying a captured
 hipGraph of the whole rollout (the graph is reusable across updates because every buffer is
@@ -45,7 +45,10 @@ class RolloutEngine:
         self.sim_mode, self.use_graph = sim_mode, use_graph
         d, H, dh, S, A, B = c.dim, c.heads, c.dim_head, c.state_dim, c.num_actions, c.num_bins
         I = H * dh
-        self.n_qkv = 3 * I + (I if c.gate_values else 0) + (H if (c.value_residual and c.learned_mix) else 0)
+        # grouped-query attention (Agent kv_heads / world_model['attn_one_kv_head']): k, v, the mix and the caches have Hkv heads
+        Hkv = self.Hkv = int(getattr(c, 'kv_heads', 0) or H)
+        Ikv = Hkv * dh
+        self.n_qkv = I + 2 * Ikv + (I if c.gate_values else 0) + (Hkv if (c.value_residual and c.learned_mix) else 0)
         ff = d * c.ff_mult
         nA = 2 * A if c.continuous else A
         f32, i32, u8 = torch.float32, torch.int32, torch.uint8
@@ -67,7 +70,7 @@ class RolloutEngine:
         self.x, self.qkv, self.att = z(E, d), z(E, self.n_qkv), z(E, I)
         glu = bool(getattr(c, 'ff_glu', False))   # world_model['ff_glu']: FF1 is the GLU projection [2 ff][d]
         self.hff, self.ac_in, self.logits, self.v1 = z(E, max(2 * ff if glu else ff, 4 * d)), z(E, c.in_dim), \
-            z(E, nA), z(E, I)
+            z(E, nA), z(E, Ikv)
         self.hglu = z(E, ff) if glu else None
         self.xn = z(E, d)
         # one-launch feed-forward (k_mlp): per 16-row panel, one FF2 partial per 128-wide hidden chunk
@@ -75,7 +78,7 @@ class RolloutEngine:
         n_chunk = ff // 128 if (ff % 128 == 0 and d % 64 == 0 and d <= 256 and not glu) else 0
         self.mlp_part = z(((E + 31) // 32) * 32 * n_chunk * d) if n_chunk else None   # (16- or 32-row panels)
         self.mlp_cnt = z((E + 15) // 16, dt=i32) if n_chunk else None
-        self.kv = [(z(E, H, Tmax, dh), z(E, H, Tmax, dh)) for _ in range(c.depth)]
+        self.kv = [(z(E, Hkv, Tmax, dh), z(E, Hkv, Tmax, dh)) for _ in range(c.depth)]
         # decode weights (nn.Linear layouts; the GEMM operands are packed from them, self.wpk)
         self.w = dict(w_pin=z(d, S), act_emb=z(A, d) if not c.continuous else z(d, A),
                       act_emb_b=z(d) if c.continuous else None, reward_embed=z(d), w_se=z(d, S), b_se=z(d),
@@ -168,6 +171,7 @@ class RolloutEngine:
         D.xpos_base = float(c.xpos_scale_base) if getattr(c, 'rotary_xpos', False) else 0.
         D.rms_norm = int(getattr(c, 'rms_norm', False))
         D.attn_window = int(getattr(c, 'attn_window', 0))   # sliding window (0: none)
+        D.Hkv = self.Hkv                                     # kv heads (grouped-query attention; = H without)
         D.sim_mode, D.hazard_log2, D.rs_eps = self.sim_mode, hazard_log2, 1e-5
         if clamp is not None:
             D.clamp_lo, D.clamp_hi, D.has_clamp = float(clamp[0]), float(clamp[1]), 1
@@ -213,7 +217,7 @@ class RolloutEngine:
             (ln_f, _, _), ffb, _ = ff_l
             wl['ln_attn'].copy_(norm_gain(ln_a))
             rows = [blk.to_q.weight, blk.to_k.weight, blk.to_v.weight]
-            bias = [torch.zeros(3 * I, device=self.dev)]
+            bias = [torch.zeros(I + 2 * c.kv_inner, device=self.dev)]
             if blk.to_v_gate is not None:
                 rows.append(blk.to_v_gate.weight)
                 bias.append(blk.to_v_gate.bias)
@@ -224,8 +228,8 @@ class RolloutEngine:
                     rows.append(blk.to_value_residual_mix[0].weight)
                     bias.append(blk.to_value_residual_mix[0].bias)
                 else:   # first layer: columns present but unused
-                    rows.append(torch.zeros(c.heads, c.dim, device=self.dev))
-                    bias.append(torch.zeros(c.heads, device=self.dev))
+                    rows.append(torch.zeros(self.Hkv, c.dim, device=self.dev))
+                    bias.append(torch.zeros(self.Hkv, device=self.dev))
             torch.cat(rows, out=wl['w_qkv'])
             torch.cat(bias, out=wl['b_qkv'][:self.n_qkv])
             wl['w_out'].copy_(blk.to_out.weight)
@@ -342,7 +346,7 @@ class RolloutEngine:
             return 0
         r4 = lambda x: (x + 3) & ~3
         d, I, ff = c.dim, c.heads * c.dim_head, c.dim * c.ff_mult   # decode.hip row_lds (in_dim <= 3 d)
-        lds = (2 * r4(d) + r4(self.n_qkv) + 2 * r4(I) + r4(max(ff, 4 * d)) + 3 * d + 4096 + r4(nA + c.num_bins)
+        lds = (2 * r4(d) + r4(self.n_qkv) + r4(I) + r4(self.Hkv * c.dim_head) + r4(max(ff, 4 * d)) + 3 * d + 4096 + r4(nA + c.num_bins)
                + c.heads * (r4(self.T) + 64) + 64)
         return 256 if 4 * lds <= 96 * 1024 else 0
 
@@ -677,6 +681,7 @@ class FractalRolloutEngine(RolloutEngine):
         super()._build_desc(clamp, hazard_log2)
         self.desc.state_only = 1
         self.desc.attn_window = 0   # (the fractal body has no sliding window)
+        self.desc.Hkv = 0           # (nor grouped-query attention)
         Lv = self.levels
         levels = (L.FractalLevel * Lv)()
         names = [n for n, _ in L.FractalLevel._fields_]

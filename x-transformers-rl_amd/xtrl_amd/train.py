@@ -82,6 +82,7 @@ class FusedTrainStep:
         self.dev = dev
         d, H, dh, L_ = c.dim, c.heads, c.dim_head, c.depth
         I, ff, B = H * dh, c.dim * c.ff_mult, c.num_bins
+        Ikv = c.kv_inner   # width of the k and v segments (grouped-query attention; = I without)
         S, A = c.state_dim, c.num_actions
         n_out = A * (2 if c.continuous else 1)
         T = b_max * n_max
@@ -115,10 +116,10 @@ class FusedTrainStep:
             wn += [pa + '1.to_value_residual_mix.0.weight'] if mix else []
             bn = ([pa + '1.to_v_gate.bias'] if c.gate_values else []) + \
                  ([pa + '1.to_value_residual_mix.0.bias'] if mix else [])
-            n_qkv = 3 * I + (I if c.gate_values else 0) + (H if mix else 0)
+            n_qkv = I + 2 * Ikv + (I if c.gate_values else 0) + (c.n_kv_heads if mix else 0)   # q | k | v | gate | mix
             max_qkv = max(max_qkv, n_qkv)
             bufs = dict(x_attn=X[li], x_ff=E(T, d), xn_attn=E(T, d), xn_ff=E(T, d), st_attn=E(T, 2), st_ff=E(T, 2),
-                        proj=E(T, n_qkv), qkv=E(T, 3 * I), o=E(T, I), lse=E(b_max * H * n_max), u=E(T, lu2),
+                        proj=E(T, n_qkv), qkv=E(T, I + 2 * Ikv), o=E(T, I), lse=E(b_max * H * n_max), u=E(T, lu2),
                         hd=E(T, lff))
             bufs['og'] = E(T, I) if c.gate_values else bufs['o']
             self.layers_py.append(bufs)
@@ -140,7 +141,7 @@ class FusedTrainStep:
                         raw=E(T, n_out), values=E(T, B), pred=E(T, 2 * (S + 1)), done=E(T),
                         d_raw=E(T, n_out), d_values=E(T, B), d_pred=E(T, 2 * (S + 1)), d_done=E(T),
                         dx=E(L_ + 1, T, d), dx2=E(L_, T, d), dxn=E(T, d), dff=E(L_, T, lu2), dproj=E(L_, T, max_qkv),
-                        dog=E(T, I), dvfirst=E(T, I),
+                        dog=E(T, I), dvfirst=E(T, Ikv),
                         dz1=E(T, 4 * d), dac=E(T, c.in_dim), dzp=E(T, ldp), dewa=E(T, 2 * d),
                         delta=E(b_max * H * n_max))
         # the library states its own partial-sum needs (LayerNorm-backward row blocks, column sums)
@@ -166,6 +167,7 @@ class FusedTrainStep:
         D.ln_final = off('transformer.attn_layers.final_norm.' + nw)
         D.rms_norm = int(c.rms_norm)
         D.attn_window = int(c.attn_window)   # sliding window (0: none)
+        D.Hkv = int(c.n_kv_heads)            # kv heads (grouped-query attention; = H without)
         D.inv_freq = self.inv_freq.data_ptr()
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
@@ -293,6 +295,7 @@ class FractalTrainStep(FusedTrainStep):
         self.dev = dev
         d, H, dh, Lv = c.dim, c.heads, c.dim_head, model.levels
         I, ff, B = H * dh, c.dim * c.ff_mult, c.num_bins
+        Ikv = c.kv_inner   # width of the k and v segments (grouped-query attention; = I without)
         S, A = c.state_dim, c.num_actions
         n_out = A * (2 if c.continuous else 1)
         T = b_max * n_max
@@ -354,6 +357,7 @@ class FractalTrainStep(FusedTrainStep):
         _heads_desc(D, c, flat)
         D.ln_final = -1
         D.attn_window = 0   # (the fractal body has no sliding window)
+        D.Hkv = 0           # (nor grouped-query attention)
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
         D.part_floats = self.buf['part'].numel()
