@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 23
+#define XTRL_ABI_VERSION 24
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -504,6 +504,8 @@ typedef struct XtrlTrainLayer {
   float* hd;            /* [T][ff] GELU + dropout output */
 } XtrlTrainLayer;
 
+typedef struct XtrlWimgEntry XtrlWimgEntry;   /* a pre-split weight image, below */
+
 typedef struct XtrlTrainDesc {
   int b, n, S, A, d, L, H, dh, ff, B, in_dim, n_out, G;
   int continuous, evolutionary, gate_values, rot_dim;
@@ -647,7 +649,43 @@ typedef struct XtrlTrainDesc {
    * value-residual mix one column per kv head and dvfirst [T][Ikv]; the attention runs as
    * xtrl_attn_fwd_gqa / xtrl_attn_bwd_part_gqa on the token rows.  0: Hkv = H */
   int Hkv;
+  /* pre-split weight images (ABI 24; optional, wimg NULL = off): the split-bf16 piece planes of the
+   * weights the warp-specialised GEMM reads as B, in the byte order its consumers read from LDS,
+   * fetched by LDS-DMA instead of being split again by every workgroup of every launch.  The table
+   * (xtrl_train_wimg_plan; wimg_tab its device copy, wimg_tab_host the host original, wimg_n
+   * entries) names each image; the arena holds wimg_bytes bytes (16-byte aligned).  xtrl_train_forward
+   * rebuilds every image from `flat` as its first launch, the backward of the same step reuses them
+   * (no optimiser step runs in between), so no caller refreshes anything.  XTRL_WIMG=0: ignored */
+  void* wimg;
+  int64_t wimg_bytes;
+  const XtrlWimgEntry* wimg_tab;
+  const XtrlWimgEntry* wimg_tab_host;
+  int wimg_n;
 } XtrlTrainDesc;
+
+/* One pre-split weight image: the B operand of a GEMM with N columns and reduction length K,
+ *   trans_b = 0: B[k][n] at flat[w_off + n ld + k]  (forward: the nn.Linear weight [N][K])
+ *   trans_b = 1: B[k][n] at flat[w_off + k ld + n]  (input gradient: the weight [K][N] read as B "T")
+ * tiled by (BN-row tile j, 32-deep K slab s): tile (j, s) is the contiguous block of
+ * XTRL_WIMG_TILE_BYTES(BN) bytes at img_off + (j ceil(K / 32) + s) * XTRL_WIMG_TILE_BYTES(BN), laid out
+ * [piece hi | mid | lo][BN rows][40] bf16: element [p][r][c], c < 32, is piece p of B[32 s + c][BN j + r]
+ * (hi = bf16-rne(x), mid = bf16-rne(x - hi), lo = bf16-rne(x - hi - mid)); rows past N, k past K and
+ * the 8 pad columns of every row are zero.  blk0: the image's first tile in the build launch. */
+struct XtrlWimgEntry {
+  int64_t w_off;
+  int64_t img_off;
+  int N, K, ld, trans_b, BN, blk0;
+};
+#define XTRL_WIMG_TILE_BYTES(BN) (3 * (BN) * 40 * 2)
+/* the images a learn step on `desc` reads (host-only): writes up to `cap` entries to tab (may be
+ * NULL), the arena bytes to *bytes, and returns the entry count (0: this model has none) */
+int xtrl_train_wimg_plan(const XtrlTrainDesc* desc, XtrlWimgEntry* tab, int cap, int64_t* bytes);
+/* builds every image of a table (tab_dev: its device copy) from `flat` into the arena, one launch */
+int xtrl_wimg_build(const float* flat, const XtrlWimgEntry* tab_host, const XtrlWimgEntry* tab_dev, int n,
+                    void* arena, int64_t arena_bytes, void* stream);
+
+/* GEMM launches of this process that read B from an image so far (host counter; tests) */
+int64_t xtrl_wimg_launch_count(void);
 
 int xtrl_train_forward(const XtrlTrainDesc* desc, void* stream);
 int xtrl_train_backward(const XtrlTrainDesc* desc, void* stream);

@@ -47,7 +47,7 @@ extern "C" int64_t xtrl_struct_size(const char* name) {
                {"XtrlTrainDesc", sizeof(XtrlTrainDesc)},     {"XtrlBatchDesc", sizeof(XtrlBatchDesc)},
                {"XtrlLossDesc", sizeof(XtrlLossDesc)},       {"XtrlFractalLevel", sizeof(XtrlFractalLevel)},
                {"XtrlFractalDesc", sizeof(XtrlFractalDesc)},     {"XtrlFractalTrainLevel", sizeof(XtrlFractalTrainLevel)},
-               {"XtrlFractalTrainDesc", sizeof(XtrlFractalTrainDesc)}};
+               {"XtrlFractalTrainDesc", sizeof(XtrlFractalTrainDesc)}, {"XtrlWimgEntry", sizeof(XtrlWimgEntry)}};
   for (const auto& s : sizes)
     if (name && strcmp(name, s.name) == 0) return s.size;
   return -1;

@@ -952,10 +952,27 @@ __device__ int g_ws_mode;   // 1: consumers skip the MFMAs; 2: producers skip lo
 // reduction — and finish the residual + LayerNorm forward, or the LayerNorm backward with the
 // incoming residual gradient and the tile's d gamma partial, in the same launch (no normalised /
 // d-normalised intermediate goes through HBM, no separate LayerNorm launch).
-template <bool TA, bool TB, int EPI, bool RES, int BM = 128, int BN = 128, bool KT = false>
+//
+// WI (B a weight with a pre-split image, GemmArgs::wimg; A "N" only): the B half of every piece image
+// is one contiguous block of the weight image (built once per optimiser step, k_wimg_build), so the
+// producers split only A and copy B's block global -> LDS by LDS-DMA (16 bytes per lane, 1 KiB per
+// wave-instruction, no registers, no ds_write).  In step t, after A's split, they issue the block of
+// slab t + 1 into image (t + 1) & 1, then A's loads of slab t + 3, and retire the DMAs with a counted
+// vmcnt that leaves those loads in flight, before a raw barrier (a __syncthreads() with a DMA pending
+// would wait vmcnt(0) and drain A's two-slab lookahead).  The consumers read image (t + 1) & 1 in step
+// t + 1, one barrier after the wait that retired it.  The image is zero past N and K: no row clamp,
+// no KT mask for B.  Same pieces, same MFMA order: bit-identical to the register-staged B.
+// Measured slower than the register-staged B in every instantiation at C3 (a slab's DMA is issued and
+// waited for inside one step: no LDS for a third B buffer), so callers pass no image
+// unless asked to (XTRL_WIMG=1 on the Python side).
+typedef __attribute__((address_space(3))) void lds_void_t;
+
+template <bool TA, bool TB, int EPI, bool RES, int BM = 128, int BN = 128, bool KT = false, bool WI = false>
 __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
   constexpr int BK = 32, XRS = BK + 8, NP = 256, TM = 2, TN = 2, WN = BN / 64;
   constexpr bool LNE = (EPI == EPI_RES_LN || EPI == EPI_LN_BWD || EPI == EPI_LN_BWD2);
+  static_assert(!WI || !TA, "weight images feed B of the A \"N\" launches");
+  static_assert(XTRL_WIMG_TILE_BYTES(BN) == 3 * BN * XRS * 2, "image tile = the B part of a piece image");
   constexpr int A_F4 = BM * BK / 4 / NP, B_F4 = BN * BK / 4 / NP;   // float4 per producer thread per slab
   constexpr int IMG = 3 * (BM + BN) * XRS;                           // bf16 per piece image
   static_assert((BM == 128 && BN == 128) || (BM == 64 && BN == 256), "tile 128 x 128 or 64 x 256");
@@ -999,17 +1016,17 @@ __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
   float rs[4] = {0.f, 0.f, 0.f, 0.f};
   // operand element loads, clamped into the operand (rows / columns past M / N feed only outputs
   // the epilogue discards; k past K: clamped in-bounds, then zeroed with KT)
+  // (KT: the zeroing waits for `convert`, two steps later — a select on the loaded value right here
+  // made the compiler wait for each slab's loads as soon as they were issued, vmcnt(0) before every
+  // barrier, which left the two-slab lookahead empty)
   auto ld_n = [&](const float* base, int64_t ld, int row, int row_lim, int k) -> float4 {   // [row][k]
-    float4 f = *reinterpret_cast<const float4*>(base + (int64_t)min(row, row_lim - 1) * ld + (KT ? min(k, K - 4) : k));
-    if constexpr (KT) {
-      const bool ok = k < K;
-      f = make_float4(ok ? f.x : 0.f, ok ? f.y : 0.f, ok ? f.z : 0.f, ok ? f.w : 0.f);
-    }
-    return f;
+    return *reinterpret_cast<const float4*>(base + (int64_t)min(row, row_lim - 1) * ld + (KT ? min(k, K - 4) : k));
   };
   auto ld_t = [&](const float* base, int64_t ld, int k, int col, int col_lim) -> float4 {   // [k][col]
-    float4 f = *reinterpret_cast<const float4*>(base + (int64_t)(KT ? min(k, K - 1) : k) * ld +
-                                                min(col, ((col_lim + 3) & ~3) - 4));
+    return *reinterpret_cast<const float4*>(base + (int64_t)(KT ? min(k, K - 1) : k) * ld +
+                                            min(col, ((col_lim + 3) & ~3) - 4));
+  };
+  auto kmask = [&](float4 f, int k) -> float4 {   // KT: a register whose reduction index k is past K holds zeros
     if constexpr (KT) {
       const bool ok = k < K;
       f = make_float4(ok ? f.x : 0.f, ok ? f.y : 0.f, ok ? f.z : 0.f, ok ? f.w : 0.f);
@@ -1028,15 +1045,31 @@ __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
         ra[S][i] = ld_t(Ab, a.lda, k0 + 4 * kq + i, m0 + 4 * q, M);
       }
     }
+    if constexpr (!WI) {
 #pragma unroll
-    for (int i = 0; i < B_F4; ++i) {
-      if constexpr (!TB) {
-        const int e = p + i * NP, r = e / (BK / 4), q = e % (BK / 4);
-        rb[S][i] = ld_n(Bb, a.ldb, n0 + r, N, k0 + 4 * q);
-      } else {   // group i / 4 covers column quads 32 (i / 4) + p / 8
-        const int kq = p % (BK / 4), q = p / (BK / 4) + 32 * (i >> 2);
-        rb[S][i] = ld_t(Bb, a.ldb, k0 + 4 * kq + (i & 3), n0 + 4 * q, N);
+      for (int i = 0; i < B_F4; ++i) {
+        if constexpr (!TB) {
+          const int e = p + i * NP, r = e / (BK / 4), q = e % (BK / 4);
+          rb[S][i] = ld_n(Bb, a.ldb, n0 + r, N, k0 + 4 * q);
+        } else {   // group i / 4 covers column quads 32 (i / 4) + p / 8
+          const int kq = p % (BK / 4), q = p / (BK / 4) + 32 * (i >> 2);
+          rb[S][i] = ld_t(Bb, a.ldb, k0 + 4 * kq + (i & 3), n0 + 4 * q, N);
+        }
       }
+    }
+  };
+  // WI: image tile (bx, slab kt) -> the B part of piece image `img`, 1 KiB chunk c by producer wave c & 3
+  // (a slab past the last repeats it, into an image no consumer reads)
+  constexpr int WB = XTRL_WIMG_TILE_BYTES(BN), WCH = WB / 1024, WPW = (WCH + 3) / 4;
+  static_assert(WB % 1024 == 0 && (3 * BM * XRS * 2) % 16 == 0, "whole wave-instructions, 16-byte aligned B part");
+  auto dma_b = [&](int kt, __bf16* img) {
+    const char* src = static_cast<const char*>(a.wimg) + ((int64_t)bx * nk + min(kt, nk - 1)) * WB + lane * 16;
+    char* dst = reinterpret_cast<char*>(img + 3 * BM * XRS);
+#pragma unroll
+    for (int i = 0; i < WPW; ++i) {
+      const int c = 4 * i + (wave - 4);
+      if (WCH % 4 == 0 || c < WCH)   // (wave-uniform)
+        __builtin_amdgcn_global_load_lds((const void*)(src + c * 1024), (lds_void_t*)(dst + c * 1024), 16, 0, 0);
     }
   };
   auto put = [&](__bf16* img, int rows, int row, int k, float4 v) {
@@ -1053,18 +1086,20 @@ __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
     *reinterpret_cast<bf16x4*>(q + rows * XRS) = m;
     *reinterpret_cast<bf16x4*>(q + 2 * rows * XRS) = l;
   };
-  auto convert = [&](auto S, __bf16* img, bool live) {   // live: a real slab (row sums count it)
+  auto convert = [&](auto S, __bf16* img, int kt, bool live) {   // slab kt; live: a real slab (row sums count it)
     __bf16* xa = img;
     __bf16* xb = img + 3 * BM * XRS;
+    const int k0 = min(kt, nk - 1) * BK;   // (as `load` clamped it)
     const int kq = p % (BK / 4), q = p / (BK / 4);
     if constexpr (!TA) {
 #pragma unroll
       for (int i = 0; i < A_F4; ++i) {
         const int e = p + i * NP, r = e / (BK / 4), qq = e % (BK / 4);
-        put(xa, BM, r, 4 * qq, ra[S][i]);
+        put(xa, BM, r, 4 * qq, kmask(ra[S][i], k0 + 4 * qq));
       }
     } else {
-      const float4 k0v = ra[S][0], k1v = ra[S][1], k2v = ra[S][2], k3v = ra[S][3];
+      const float4 k0v = kmask(ra[S][0], k0 + 4 * kq), k1v = kmask(ra[S][1], k0 + 4 * kq + 1),
+                   k2v = kmask(ra[S][2], k0 + 4 * kq + 2), k3v = kmask(ra[S][3], k0 + 4 * kq + 3);
       put(xa, BM, 4 * q + 0, 4 * kq, make_float4(k0v.x, k1v.x, k2v.x, k3v.x));
       put(xa, BM, 4 * q + 1, 4 * kq, make_float4(k0v.y, k1v.y, k2v.y, k3v.y));
       put(xa, BM, 4 * q + 2, 4 * kq, make_float4(k0v.z, k1v.z, k2v.z, k3v.z));
@@ -1080,17 +1115,19 @@ __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
         }
       }
     }
-    if constexpr (!TB) {
+    if constexpr (WI) {   // B arrives by dma_b
+    } else if constexpr (!TB) {
 #pragma unroll
       for (int i = 0; i < B_F4; ++i) {
         const int e = p + i * NP, r = e / (BK / 4), qq = e % (BK / 4);
-        put(xb, BN, r, 4 * qq, rb[S][i]);
+        put(xb, BN, r, 4 * qq, kmask(rb[S][i], k0 + 4 * qq));
       }
     } else {
 #pragma unroll
       for (int gi = 0; gi < B_F4 / 4; ++gi) {
         const int qg = q + 32 * gi;
-        const float4 k0v = rb[S][4 * gi], k1v = rb[S][4 * gi + 1], k2v = rb[S][4 * gi + 2], k3v = rb[S][4 * gi + 3];
+        const float4 k0v = kmask(rb[S][4 * gi], k0 + 4 * kq), k1v = kmask(rb[S][4 * gi + 1], k0 + 4 * kq + 1),
+                     k2v = kmask(rb[S][4 * gi + 2], k0 + 4 * kq + 2), k3v = kmask(rb[S][4 * gi + 3], k0 + 4 * kq + 3);
         put(xb, BN, 4 * qg + 0, 4 * kq, make_float4(k0v.x, k1v.x, k2v.x, k3v.x));
         put(xb, BN, 4 * qg + 1, 4 * kq, make_float4(k0v.y, k1v.y, k2v.y, k3v.y));
         put(xb, BN, 4 * qg + 2, 4 * kq, make_float4(k0v.z, k1v.z, k2v.z, k3v.z));
@@ -1156,12 +1193,32 @@ __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
   // (clamped); their splits go to images no consumer reads.  (Three register sets with the loads
   // issued ahead of the split measured 13 % slower: tools/ws_lab.hip.)
   const int nsteps = 2 * ((nk + 1) / 2);
+  // WI: the producers' barrier.  The A_F4 loads of A issued after the DMAs stay in flight; the DMAs
+  // (older in the in-order vmcnt) and this wave's piece stores retire.  The builtin tells the compiler's
+  // own wait insertion what has retired, the asm is the wait that is certainly there.
+  auto wi_barrier = [&]() {
+    static_assert(A_F4 <= 15, "vmcnt immediate");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(A_F4 | 0x70);   // vmcnt(A_F4) lgkmcnt(0), expcnt untouched
+    if constexpr (A_F4 == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+    static_assert(A_F4 == 2 || A_F4 == 4, "vmcnt immediates above");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  };
   if (producer) {
     load(I0{}, 0);
     load(I1{}, 1);
-    convert(I0{}, smem, true);
+    convert(I0{}, smem, 0, true);
+    if constexpr (WI) {
+      __builtin_amdgcn_sched_barrier(0);
+      dma_b(0, smem);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     load(I0{}, 2);
-    __syncthreads();
+    if constexpr (WI) wi_barrier();
+    else __syncthreads();
 #ifdef XTRL_WS_DIAG
     const int mode = g_ws_mode;
 #elif defined(XTRL_WS_MODE)   // tools/ws_lab.hip stamp-free builds: the same modes, fixed at compile time
@@ -1173,8 +1230,18 @@ __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
     // scheduling barriers keep each step's split inside its step (the scheduler would otherwise
     // hoist the next step's split arithmetic above the workgroup barrier)
     auto pstep = [&](auto C, int t) {
+      if constexpr (WI) {
+        __bf16* img = smem + ((t + 1) & 1) * IMG;
+        convert(C, img, t + 1, t + 1 < nk);
+        __builtin_amdgcn_sched_barrier(0);
+        dma_b(t + 1, img);
+        __builtin_amdgcn_sched_barrier(0);
+        load(C, t + 3);
+        wi_barrier();
+        return;
+      }
       WS_STAMP(t, 0);
-      if (mode < 2 || mode == 4) convert(C, smem + ((t + 1) & 1) * IMG, t + 1 < nk);
+      if (mode < 2 || mode == 4) convert(C, smem + ((t + 1) & 1) * IMG, t + 1, t + 1 < nk);
       else if (mode == 3) {   // consume the loads without splitting
         float s = 0.f;
 #pragma unroll
@@ -1439,12 +1506,30 @@ bool ws_ok(const GemmArgs& a, bool ta, bool ln) {
   return wgs <= 256 && (a.kspan > 0 ? a.kspan : a.K) >= (ta ? 64 : 512);
 }
 
+int64_t g_wimg_launches = 0;   // image-fed launches so far (xtrl_wimg_launch_count: tests check the path is taken)
+
+bool wimg_on() {   // XTRL_WIMG=0: no pre-split weight images (A/B experiments)
+  static const bool on = [] {
+    const char* e = getenv("XTRL_WIMG");
+    return !(e && atoi(e) == 0);
+  }();
+  return on;
+}
+
+// B from its pre-split image (GemmArgs::wimg) when the launch has one tiled for this kernel's BN rows
 template <bool TA, bool TB, int EPI, bool RES, int BM = 128, int BN = 128, bool KT = false>
 void launch_ws(const GemmArgs& a, hipStream_t s) {
   const int splits = a.kspan > 0 ? (a.K + a.kspan - 1) / a.kspan : 1;
   dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, splits);
   GemmArgs r = a;
   r.xcd_remap = (xcd_env() && (int64_t)grid.x * grid.y * grid.z % 8 == 0) ? 1 : 0;
+  if constexpr (!TA && (EPI == EPI_NONE || EPI == EPI_RES_LN || EPI == EPI_LN_BWD || EPI == EPI_LN_BWD2)) {
+    if (a.wimg && a.wimg_bn == BN && a.kspan == 0 && wimg_on()) {
+      ++g_wimg_launches;
+      hipLaunchKernelGGL((k_gemm_ws<TA, TB, EPI, RES, BM, BN, KT, true>), grid, dim3(512), 0, s, r);
+      return;
+    }
+  }
   hipLaunchKernelGGL((k_gemm_ws<TA, TB, EPI, RES, BM, BN, KT>), grid, dim3(512), 0, s, r);
 }
 
@@ -1996,7 +2081,98 @@ int layernorm_f32(const float* X, int ldx, const float* gamma, float* Y, int ldy
   return XTRL_OK;
 }
 
+// ---- pre-split weight images (XtrlWimgEntry, include/xtrl_hip.h; k_gemm_ws WI) -------------------
+// One workgroup per image tile (BN rows x one 32-deep K slab) of any entry of the table: a thread
+// takes four consecutive k of one row (forward orientation: a float4 of the weight row, 8 threads per
+// row; transposed: four rows of the weight, consecutive threads along n), splits them with split3 —
+// the producers' own split — and stores the three bf16x4 pieces where the producers' `put` would;
+// rows past N and k past K are stored as zeros, and so are the 8 pad columns of every row.
+namespace {
+__global__ __launch_bounds__(256) void k_wimg_build(const float* __restrict__ flat, const XtrlWimgEntry* __restrict__ tab,
+                                                    int n, char* __restrict__ arena) {
+  constexpr int BK = 32, XRS = BK + 8;
+  int e = 0;
+  while (e + 1 < n && tab[e + 1].blk0 <= (int)blockIdx.x) ++e;
+  const XtrlWimgEntry E = tab[e];
+  const int BN = E.BN, nkt = (E.K + BK - 1) / BK, blk = (int)blockIdx.x - E.blk0, j = blk / nkt, s = blk % nkt;
+  __bf16* out = reinterpret_cast<__bf16*>(arena + E.img_off + (int64_t)blk * XTRL_WIMG_TILE_BYTES(BN));
+  const float* W = flat + E.w_off;
+  for (int u = threadIdx.x; u < BN * (BK / 4); u += 256) {
+    const int r = E.trans_b ? u % BN : u / (BK / 4), q = E.trans_b ? u / BN : u % (BK / 4);
+    const int row = j * BN + r, k0 = s * BK + 4 * q;
+    float v[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const bool ok = row < E.N && k0 + c < E.K;
+      const int64_t at = E.trans_b ? (int64_t)(k0 + c) * E.ld + row : (int64_t)row * E.ld + k0 + c;
+      const float x = W[ok ? at : 0];   // (every load in bounds, the value selected afterwards)
+      v[c] = ok ? x : 0.f;
+    }
+    bf16x4 h, m, l;
+    split3(make_float4(v[0], v[1], v[2], v[3]), h, m, l);
+    __bf16* o = out + r * XRS + 4 * q;
+    *reinterpret_cast<bf16x4*>(o) = h;
+    *reinterpret_cast<bf16x4*>(o + BN * XRS) = m;
+    *reinterpret_cast<bf16x4*>(o + 2 * BN * XRS) = l;
+    if (q == 0) {
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc)
+        *reinterpret_cast<uint4*>(out + (pc * BN + r) * XRS + BK) = make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
+}
+}  // namespace
+
+bool wimg_enabled() { return wimg_on(); }
+
+int wimg_tile_bn(int N, int epi) {
+  const bool lne = epi == EPI_RES_LN || epi == EPI_LN_BWD || epi == EPI_LN_BWD2;
+  return lne && N > 128 ? 256 : 128;
+}
+
+void wimg_find(GemmArgs& g, int trans_b, int epi, const float* flat, const XtrlWimgEntry* tab, int n,
+               const void* arena) {
+  if (!tab || !arena || n <= 0 || !wimg_on()) return;
+  const int bn = wimg_tile_bn(g.N, epi);
+  for (int i = 0; i < n; ++i) {
+    const XtrlWimgEntry& E = tab[i];
+    if (flat + E.w_off == g.B && E.trans_b == trans_b && E.N == g.N && E.K == g.K && E.ld == g.ldb && E.BN == bn) {
+      g.wimg = static_cast<const char*>(arena) + E.img_off;
+      g.wimg_bn = bn;
+      return;
+    }
+  }
+}
+
+int wimg_build(const float* flat, const XtrlWimgEntry* tab_host, const XtrlWimgEntry* tab_dev, int n, void* arena,
+               int64_t arena_bytes, hipStream_t s) {
+  XTRL_REQUIRE(flat && tab_host && tab_dev && arena && n > 0, "wimg: null table / arena");
+  XTRL_REQUIRE(((uintptr_t)arena & 15u) == 0, "wimg: the arena must be 16-byte aligned");
+  int blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const XtrlWimgEntry& E = tab_host[i];
+    XTRL_REQUIRE((E.BN == 128 || E.BN == 256) && E.N > 0 && E.K > 0 && E.w_off >= 0 && E.img_off >= 0 &&
+                     E.img_off % 16 == 0 && E.blk0 == blocks && (E.trans_b == 0 || E.trans_b == 1) &&
+                     E.ld >= (E.trans_b ? E.N : E.K),
+                 "wimg: bad table entry %d", i);
+    const int64_t tiles = (int64_t)((E.N + E.BN - 1) / E.BN) * ((E.K + 31) / 32);
+    XTRL_REQUIRE(E.img_off + tiles * XTRL_WIMG_TILE_BYTES(E.BN) <= arena_bytes,
+                 "wimg: entry %d ends past the arena (%lld bytes)", i, (long long)arena_bytes);
+    blocks += (int)tiles;
+  }
+  hipLaunchKernelGGL(k_wimg_build, dim3(blocks), dim3(256), 0, s, flat, tab_dev, n, static_cast<char*>(arena));
+  XTRL_LAUNCHED("wimg_build");
+  return XTRL_OK;
+}
+
 }  // namespace xtrl
+
+extern "C" int64_t xtrl_wimg_launch_count(void) { return xtrl::g_wimg_launches; }
+
+extern "C" int xtrl_wimg_build(const float* flat, const XtrlWimgEntry* tab_host, const XtrlWimgEntry* tab_dev, int n,
+                               void* arena, int64_t arena_bytes, void* stream) {
+  return xtrl::wimg_build(flat, tab_host, tab_dev, n, arena, arena_bytes, xtrl::as_stream(stream));
+}
 
 extern "C" int xtrl_gemm_f32(const float* X, int ldx, const float* W, int ldw, const float* bias,
                              const float* ln_gamma, const float* R, int ldr, float* Y, int ldy,

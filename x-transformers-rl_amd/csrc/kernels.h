@@ -85,7 +85,21 @@ struct GemmArgs {
   float* ln2_out = nullptr;
   float* ln2_part = nullptr;
   float* ln2_part_b = nullptr;
+  // pre-split image of B (wimg_find; XtrlWimgEntry in include/xtrl_hip.h), tiled for wimg_bn-row tiles:
+  // the warp-specialised kernel's producers fetch B's piece planes by LDS-DMA instead of splitting B.
+  // NULL, or a launch that does not go to that kernel: B is read from `B` as ever
+  const void* wimg = nullptr;
+  int wimg_bn = 0;
 };
+// the image of the B operand (B, ldb, N, K, trans_b) in a table of n entries over `flat`, if it has one
+// whose tiles suit the kernel this GEMM goes to (epi: a LayerNorm epilogue's tile is gemm_ln_rows' partner)
+void wimg_find(GemmArgs& g, int trans_b, int epi, const float* flat, const XtrlWimgEntry* tab, int n,
+               const void* arena);
+// rows of B per image tile for a GEMM of N columns with this epilogue (128 or 256)
+int wimg_tile_bn(int N, int epi);
+bool wimg_enabled();   // XTRL_WIMG=0 turns the images off
+int wimg_build(const float* flat, const XtrlWimgEntry* tab_host, const XtrlWimgEntry* tab_dev, int n, void* arena,
+               int64_t arena_bytes, hipStream_t s);
 // rows per workgroup of the LayerNorm-epilogue GEMM for an N-column row (the column tile is the row)
 int gemm_ln_rows(int N);
 

@@ -902,6 +902,10 @@ struct Ctx {
   SplitKQueue* q = nullptr;   // weight gradients: split-K reductions deferred to one launch
   const float* P(int64_t off) const { return off >= 0 ? D->flat + off : nullptr; }
   float* G(int64_t off) const { return off >= 0 ? D->grad + off : nullptr; }
+  // B's pre-split image, when the step has one for this weight view (XtrlTrainDesc.wimg)
+  void img(GemmArgs& g, int trans_b, int epi) const {
+    wimg_find(g, trans_b, epi, D->flat, D->wimg_tab_host, D->wimg_n, D->wimg);
+  }
 };
 
 // row stride of the [T][ff] feed-forward buffers (hd, u, dff; fractal h, u, dz): ld_ff >= ff, 0 = ff
@@ -1027,6 +1031,7 @@ int linear_fwd(const Ctx& c, const float* A, int lda, const float* W, const floa
     g.drop_thresh8 = dropout_thresh8(c.D->dropout);
     g.inv_keep = c.D->dropout > 0.f ? 1.f / (1.f - c.D->dropout) : 1.f;
   }
+  c.img(g, 0, epi);
   return gemm_run(g, 0, 0, epi, c.s);
 }
 
@@ -1038,6 +1043,7 @@ int linear_dgrad(const Ctx& c, const float* dY, int ldy, const float* W, float* 
   g.A = dY; g.lda = ldy; g.B = W; g.ldb = K; g.C = dX; g.ldc = ldx; g.M = M; g.N = K; g.K = N;
   g.aux_in = aux_in; g.ld_aux_in = ld_aux; g.act_cols = act_cols;
   g.aux_in2 = aux_in2; g.ld_aux_in2 = ld_aux2; g.aux_out = aux_out; g.ld_aux_out = ld_aux_out;
+  c.img(g, 1, epi);
   return gemm_run(g, 0, 1, epi, c.s);
 }
 
@@ -1117,6 +1123,7 @@ int linear_res_ln(const Ctx& c, const float* A, int lda, const float* W, const f
   g.A = A; g.lda = lda; g.B = W; g.ldb = K; g.bias = bias; g.C = x_out; g.ldc = d; g.M = c.T; g.N = d; g.K = K;
   g.R = R; g.ldr = d; g.ln_g = gamma; g.ln_y1 = y1; g.ln_ld1 = ld1; g.ln_y2 = y2; g.ln_ld2 = ld2; g.ln_stats = st;
   g.ln_rms = c.D->rms_norm;
+  c.img(g, 0, EPI_RES_LN);
   return gemm_run(g, 0, 0, EPI_RES_LN, c.s);
 }
 
@@ -1133,6 +1140,7 @@ int dgrad_ln_bwd(const Ctx& c, const float* dY, int ldy, const float* W, int N, 
   g.A = dY; g.lda = ldy; g.B = W; g.ldb = d; g.C = dx; g.ldc = d; g.M = c.T; g.N = d; g.K = N;
   g.ln_g = gamma; g.ln_x = x; g.ln_stats = const_cast<float*>(st); g.ln_dres = dres; g.ln_part = P ? P : c.D->part;
   g.ln_rms = c.D->rms_norm;
+  c.img(g, 1, EPI_LN_BWD);
   if ((rc = gemm_run(g, 0, 1, EPI_LN_BWD, c.s))) return rc;
   if (!P)
     hipLaunchKernelGGL(k_colsum_final, dim3(blocks(d, CS_COLS)), dim3(64 * CS_WAVES), 0, c.s, c.D->part, nb, d, dgamma);
@@ -1360,6 +1368,7 @@ int heads_backward(const Ctx& c, const Ctx& cw, Fork& F, bool embed_cols = true)
     GemmArgs g;
     g.A = D->dz1; g.lda = 4 * d; g.B = c.P(D->w_h1) + d; g.ldb = D->in_dim; g.C = D->dac + d; g.ldc = D->in_dim;
     g.M = T; g.N = D->in_dim - d; g.K = 4 * d;
+    c.img(g, 1, EPI_NONE);
     if ((rc = gemm_run(g, 0, 1, EPI_NONE, c.s))) return rc;
   }
   // state embedding and gene conditioning
@@ -1404,6 +1413,10 @@ int train_forward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
   const int T = c.T, d = D->d, I = D->H * D->dh, ff = D->ff, lf = ld_ff(D);
   const int Ikv = kv_inner(D), nq3 = I + 2 * Ikv;   // the k / v segment width; q | k | v columns of a projection row
   int rc;
+  // the pre-split weight images, from the parameters this step is about to read: first on the stream,
+  // reused by this step's backward (XTRL_WIMG=0: none; the lookups then find nothing either)
+  if (D->wimg && D->wimg_tab && D->wimg_tab_host && D->wimg_n > 0 && wimg_enabled())
+    if ((rc = wimg_build(D->flat, D->wimg_tab_host, D->wimg_tab, D->wimg_n, D->wimg, D->wimg_bytes, s))) return rc;
   // embeddings
   if (D->evolutionary) {
     hipLaunchKernelGGL(k_latent_embed, dim3(blocks(D->b * d, 256)), dim3(256), 0, s, D->latent, c.P(D->w_lat),
@@ -1551,6 +1564,7 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     float* P = csq.take_or_flush(nb, d, c.G(D->ln_final), s, &rc);
     if (rc) return rc;
     g.ln_gpre = D->dewa; g.ln_ldg = 2 * d; g.ln_gscale = D->frac_head_grad; g.ln_part = P ? P : D->part;
+    c.img(g, 1, EPI_LN_BWD2);
     if ((rc = gemm_run(g, 0, 1, EPI_LN_BWD2, s))) return rc;
     if (!P)
       hipLaunchKernelGGL(k_colsum_final, dim3(blocks(d, CS_COLS)), dim3(64 * CS_WAVES), 0, s, D->part, nb, d,
@@ -2226,6 +2240,42 @@ extern "C" int64_t xtrl_train_part_floats(int T, int b, int d, int A) {
   const int64_t lat = (int64_t)std::max(b, 1) * d;                                      // latent gradient
   const int64_t emb = (int64_t)std::max(A, 1) * d;                                      // >= 1 embedding chunk
   return std::max(std::max(ln, cs), std::max(lat, emb));
+}
+
+// The weight views the decoder step's warp-specialised GEMMs read as B (fused LayerNorms): per block
+// the out-projection and FF2 forward (residual + LayerNorm epilogue), FF1 and the q|k|v projection as
+// input gradients (LayerNorm-backward epilogue); the actor | critic first layer as the final norm's
+// input gradient (its embed columns) and as the plain input gradient of the other columns.  Only the
+// orientation such a launch reads is built: the other GEMMs of a weight take the register-staged
+// kernel, which reads no image.
+extern "C" int xtrl_train_wimg_plan(const XtrlTrainDesc* D, XtrlWimgEntry* tab, int cap, int64_t* bytes) {
+  int n = 0, blk = 0;
+  int64_t at = 0;
+  auto add = [&](int64_t w_off, int trans_b, int N, int K, int ld, int epi) {
+    if (w_off < 0 || N <= 0 || K <= 0) return;
+    XtrlWimgEntry E{};
+    E.w_off = w_off; E.img_off = at; E.N = N; E.K = K; E.ld = ld; E.trans_b = trans_b;
+    E.BN = xtrl::wimg_tile_bn(N, epi); E.blk0 = blk;
+    const int64_t tiles = (int64_t)((N + E.BN - 1) / E.BN) * ((K + 31) / 32);
+    if (tab && n < cap) tab[n] = E;
+    ++n;
+    blk += (int)tiles;
+    at += tiles * XTRL_WIMG_TILE_BYTES(E.BN);
+  };
+  if (D && D->layers && D->L > 0 && D->d > 0 && xtrl::ln_fusable(D)) {
+    const int d = D->d, I = D->H * D->dh, f1 = D->ff_glu ? 2 * D->ff : D->ff;
+    for (int li = 0; li < D->L; ++li) {
+      const XtrlTrainLayer& Ly = D->layers[li];
+      add(Ly.w_out, 0, d, I, I, xtrl::EPI_RES_LN);
+      add(Ly.w_ff2, 0, d, D->ff, D->ff, xtrl::EPI_RES_LN);
+      add(Ly.w_ff1, 1, d, f1, d, xtrl::EPI_LN_BWD);
+      add(Ly.w_proj, 1, d, Ly.n_qkv, d, xtrl::EPI_LN_BWD);
+    }
+    add(D->w_h1, 1, d, 4 * d, D->in_dim, xtrl::EPI_LN_BWD2);
+    if (D->w_h1 >= 0) add(D->w_h1 + d, 1, D->in_dim - d, 4 * d, D->in_dim, xtrl::EPI_NONE);
+  }
+  if (bytes) *bytes = at;
+  return n;
 }
 
 extern "C" int64_t xtrl_train_pack_floats(int T, int S, int A, int n_out, int B) {

@@ -13,7 +13,7 @@ from pathlib import Path
 import torch   # noqa: F401  (load torch's HIP runtime first so the library binds to the same one)
 
 LIB_PATH = Path(os.environ.get('XTRL_LIB', Path(__file__).resolve().parent / 'libxtrl_hip.so'))   # override: A/B experiments
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 P = C.c_void_p
 I32, I64, U32, U64, F32 = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
@@ -86,6 +86,20 @@ class TrainLayer(C.Structure):
                                     'lse', 'u', 'hd')])
 
 
+class WimgEntry(C.Structure):
+    """One pre-split weight image (XtrlWimgEntry): the B operand view, its tile rows and its place in the arena."""
+    _fields_ = [('w_off', I64), ('img_off', I64), ('N', I32), ('K', I32), ('ld', I32), ('trans_b', I32), ('BN', I32),
+                ('blk0', I32)]
+
+
+WIMG_XRS = 40   # bf16 per image row: a 32-deep K slab + 8 pad columns
+
+
+def wimg_tile_bytes(bn: int) -> int:
+    """Bytes of one image tile [hi | mid | lo][bn rows][40] bf16 (XTRL_WIMG_TILE_BYTES)."""
+    return 3 * bn * WIMG_XRS * 2
+
+
 class TrainDesc(C.Structure):
     _fields_ = ([(n, I32) for n in ('b', 'n', 'S', 'A', 'd', 'L', 'H', 'dh', 'ff', 'B', 'in_dim', 'n_out', 'G',
                                     'continuous', 'evolutionary', 'gate_values', 'rot_dim')]
@@ -107,7 +121,8 @@ class TrainDesc(C.Structure):
                    ('Tv', I32), ('vrows', P), ('vinv', P), ('ewa_v', P), ('hp_v', P), ('zp_v', P), ('pred_v', P),
                    ('d_pred_v', P), ('dzp_v', P), ('dewa_v', P), ('dq_part', P), ('dq_part_floats', I64),
                    ('packed', I32), ('ep_off', P), ('pack_ws', P), ('pack_ws_floats', I64), ('attn_window', I32),
-                   ('Hkv', I32)])
+                   ('Hkv', I32), ('wimg', P), ('wimg_bytes', I64), ('wimg_tab', P),
+                   ('wimg_tab_host', C.POINTER(WimgEntry)), ('wimg_n', I32)])
 
 
 class FractalTrainLevel(C.Structure):
@@ -189,6 +204,9 @@ SIGNATURES = {
     'xtrl_train_backward': (I32, [C.POINTER(TrainDesc), P]),
     'xtrl_ff_dropout_mask': (I32, [P, I32, I32, F32, U64, U32, U32, P]),
     'xtrl_train_part_floats': (C.c_int64, [I32, I32, I32, I32]),
+    'xtrl_train_wimg_plan': (I32, [C.POINTER(TrainDesc), C.POINTER(WimgEntry), I32, C.POINTER(I64)]),
+    'xtrl_wimg_launch_count': (I64, []),
+    'xtrl_wimg_build': (I32, [P, C.POINTER(WimgEntry), P, I32, P, I64, P]),
     'xtrl_minibatch_gather': (I32, [C.POINTER(BatchDesc), P]),
     'xtrl_rsnorm_update': (I32, [P, P, P, I32, I32, P]),
     'xtrl_attn_fwd_tokens': (I32, [P, I32, P, I32, P, I32, P, P, I32, P, I32, I32, I32, I32, F32, I32, P]),
@@ -207,7 +225,8 @@ SIGNATURES = {
 STRUCTS = {'XtrlDecodeLayer': DecodeLayer, 'XtrlRngState': RngState, 'XtrlDecodeDesc': DecodeDesc,
            'XtrlTrainLayer': TrainLayer, 'XtrlTrainDesc': TrainDesc, 'XtrlBatchDesc': BatchDesc,
            'XtrlLossDesc': LossDesc, 'XtrlFractalLevel': FractalLevel, 'XtrlFractalDesc': FractalDesc,
-           'XtrlFractalTrainLevel': FractalTrainLevel, 'XtrlFractalTrainDesc': FractalTrainDesc}
+           'XtrlFractalTrainLevel': FractalTrainLevel, 'XtrlFractalTrainDesc': FractalTrainDesc,
+           'XtrlWimgEntry': WimgEntry}
 
 _lib = None
 

@@ -9,11 +9,16 @@ every minibatch; gradients are accumulated into the flat gradient buffer of ``Fl
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
 from . import _lib as L
 from .params import FlatParams
+
+
+# XTRL_WIMG=1: the learn step reads its weights' pre-split images (read once; default off, see FusedTrainStep)
+WIMG_DEFAULT = os.environ.get('XTRL_WIMG', '0') == '1'
 
 
 def ld_ff(ff):
@@ -54,6 +59,23 @@ def _compact_bufs(D, c, T, dev, b_max, n_max):
         bufs['dq_part'] = torch.empty(nf, **f32)
         D.dq_part, D.dq_part_floats = bufs['dq_part'].data_ptr(), nf
     return bufs
+
+
+def _alloc_wimg(D, dev):
+    """The arena and table of the pre-split weight images (XtrlTrainDesc.wimg): the library plans them from the
+    filled descriptor and rebuilds the images in every forward; here only the allocation and the table's
+    device copy.  None when the step reads no image."""
+    nbytes = C.c_int64(0)
+    n = int(L.lib().xtrl_train_wimg_plan(C.byref(D), None, 0, C.byref(nbytes)))
+    if n <= 0 or nbytes.value <= 0:
+        return None
+    tab = (L.WimgEntry * n)()
+    L.lib().xtrl_train_wimg_plan(C.byref(D), tab, n, C.byref(nbytes))
+    arena = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+    D.wimg, D.wimg_bytes = arena.data_ptr(), nbytes.value
+    D.wimg_tab, D.wimg_tab_host, D.wimg_n = tab_dev.data_ptr(), C.cast(tab, C.POINTER(L.WimgEntry)), n
+    return dict(tab=tab, tab_dev=tab_dev, arena=arena)
 
 
 def _heads_desc(D, c, flat):
@@ -179,6 +201,27 @@ class FusedTrainStep:
         D.ff_glu, D.ld_u2 = int(glu), (lu2 if glu else 0)
         self.cbuf = _compact_bufs(D, c, T, dev, b_max, n_max)
         self.D = D
+        # pre-split weight images: off unless asked for (XTRL_WIMG=1, or use_weight_images(True)) — on the
+        # C3 step every image-fed GEMM measured slower than the register-staged one
+        self.wimg = None
+        if WIMG_DEFAULT:
+            self.use_weight_images(True)
+
+    def use_weight_images(self, on: bool):
+        """Pre-split weight images on / off for the following steps (off: the descriptor without its arena —
+        the library's image-free path; tests and A/B runs compare the two in one process).  The arena and
+        the table are allocated on first use."""
+        D = self.D
+        if not on or isinstance(self, FractalTrainStep):   # (the fractal step plans no images)
+            D.wimg, D.wimg_bytes, D.wimg_tab, D.wimg_tab_host, D.wimg_n = None, 0, None, None, 0
+            return
+        if self.wimg is None:
+            self.wimg = _alloc_wimg(D, self.dev)
+        w = self.wimg
+        if w is not None:
+            D.wimg, D.wimg_bytes = w['arena'].data_ptr(), w['arena'].numel()
+            D.wimg_tab, D.wimg_tab_host, D.wimg_n = w['tab_dev'].data_ptr(), C.cast(w['tab'], C.POINTER(L.WimgEntry)), \
+                len(w['tab'])
 
     # ------------------------------------------------------------------------------------------
     def forward(self, swr, prev_action, next_action, latent, lens, reward_keep, seed, attn_offset, ff_offset,
