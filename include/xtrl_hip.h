@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 24
+#define XTRL_ABI_VERSION 25
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -112,6 +112,10 @@ typedef struct XtrlDecodeLayer {
    * and splits the weight fragments into their bf16 pieces itself — the same pieces, bit-identical */
   const float* w_ff1f;
   const float* w_ff2f;
+  /* attention sinks (ABI 25; XtrlDecodeDesc.num_mem_kv > 0): the layer's memory keys / values
+   * [Hkv][num_mem_kv][dh] (plain fp32, the parameters themselves), else NULL */
+  const float* mem_k;
+  const float* mem_v;
 } XtrlDecodeLayer;
 
 typedef struct XtrlRngState {   /* device memory; read by the sampling / sim kernels */
@@ -244,6 +248,12 @@ typedef struct XtrlDecodeDesc {
    * [E][Ikv]: the resident cache and the cache read shrink by H / Hkv.  0: Hkv = H (a zero-initialised
    * descriptor is plain multi-head attention) */
   int Hkv;
+  /* attention sinks (ABI 25): world_model['attn_num_mem_kv'] learned memory key / value rows per kv head
+   * (XtrlDecodeLayer.mem_k / mem_v; no rotary) and world_model['attn_add_zero_kv'], one all-zero key /
+   * value ("+ 1" in the softmax denominator).  The step-t query attends its cached keys (the window's)
+   * plus the sinks; they are never cached and not counted in the window.  0 / 0: none */
+  int num_mem_kv;
+  int add_zero_kv;
 } XtrlDecodeDesc;
 
 /* Reset: state_0 = sim reset, prev_action = -1 / 0, prev_reward = 0, alive = 1, lens = 0, and
@@ -467,6 +477,37 @@ int xtrl_attn_bwd_part_gqa(const float* q, const float* k, const float* v, const
                            const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
                            float* dq_part, int64_t dq_part_floats, int b, int H, int Hkv, int n, int dh, float scale,
                            float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, int window, void* stream);
+/* The three _gqa entry points with attention sinks (x-transformers Attention num_mem_kv / add_zero_kv;
+ * ABI 25): mem_k, mem_v [Hkv][num_mem_kv][dh] (0 <= num_mem_kv <= 16) are key / value rows every query
+ * row of the kv head's query heads sees, and add_zero_kv != 0 adds one all-zero key / value — whatever the
+ * causal, padding or window mask says, padded rows included, without rotary:
+ *   L_i = sum_{visible j} exp(s_ij) + sum_m exp(scale q_i . mem_k[g, m]) + add_zero_kv,  lse_i = log L_i,
+ *   o_i = sum_j z_ij P_ij v_j + sum_m z'_im P_im mem_v[g, m]                      (g = h % Hkv)
+ * so a row without a visible real key attends the sinks alone (the window's uniform rule for such rows
+ * does not apply).  The real keys' keep bits z are those of the _gqa entry points; z'_im keeps iff word
+ * (i & 3) of philox(seed; i >> 2, 0x80000000 | m, offset + b H + h, c3) >= dropout_p 2^32, c3 the call's own
+ * ((7 << 24) | sub, with bit 23 set when 256 dropout_p is an integer).  Backward: dq includes the sink
+ * term; dmem_k, dmem_v [Hkv][num_mem_kv][dh] are stored (not accumulated), summed over b, the kv head's
+ * query heads and the rows in a fixed order (no atomics) through sink_ws, xtrl_attn_sink_ws_floats(b, H,
+ * num_mem_kv, dh) floats.  num_mem_kv = 0 needs none of the pointers; with add_zero_kv = 0 as well these
+ * are the _gqa entry points (which call them so), bit for bit. */
+int64_t xtrl_attn_sink_ws_floats(int b, int H, int num_mem_kv, int dh);
+int xtrl_attn_fwd_sink(const float* q, const float* k, const float* v, const int32_t* lens, float* o, float* lse,
+                       const float* mem_k, const float* mem_v, int b, int H, int Hkv, int n, int dh, float scale,
+                       float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, int window, int num_mem_kv,
+                       int add_zero_kv, void* stream);
+int xtrl_attn_bwd_sink(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                       const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                       const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v, float* sink_ws,
+                       int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh, float scale, float dropout_p,
+                       uint64_t seed, uint32_t offset, uint32_t sub, int window, int num_mem_kv, int add_zero_kv,
+                       void* stream);
+int xtrl_attn_bwd_part_sink(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                            const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                            float* dq_part, int64_t dq_part_floats, const float* mem_k, const float* mem_v,
+                            float* dmem_k, float* dmem_v, float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv,
+                            int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
+                            int window, int num_mem_kv, int add_zero_kv, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Learn-step forward / backward of WorldModelActorCritic on one minibatch, hand-scheduled (no
@@ -502,6 +543,7 @@ typedef struct XtrlTrainLayer {
   float* lse;           /* [b][H][n] */
   float* u;             /* [T][ff] FF1 local derivative: dropout-masked GELU'(pre-activation) */
   float* hd;            /* [T][ff] GELU + dropout output */
+  int64_t mem_k, mem_v; /* attention sinks (ABI 25): the memory keys / values [Hkv][num_mem_kv][dh] in flat; -1: none */
 } XtrlTrainLayer;
 
 typedef struct XtrlWimgEntry XtrlWimgEntry;   /* a pre-split weight image, below */
@@ -661,6 +703,14 @@ typedef struct XtrlTrainDesc {
   const XtrlWimgEntry* wimg_tab;
   const XtrlWimgEntry* wimg_tab_host;
   int wimg_n;
+  /* attention sinks (ABI 25), as XtrlDecodeDesc: num_mem_kv memory key / value rows per kv head at
+   * XtrlTrainLayer.mem_k / mem_v (their gradients land at the same offsets of grad, inside the layer's
+   * bucket) and add_zero_kv; the attention runs as xtrl_attn_fwd_sink / xtrl_attn_bwd_part_sink on the
+   * token rows.  sink_ws: xtrl_attn_sink_ws_floats(b, H, num_mem_kv, dh) floats (num_mem_kv > 0) */
+  int num_mem_kv;
+  int add_zero_kv;
+  float* sink_ws;
+  int64_t sink_ws_floats;
 } XtrlTrainDesc;
 
 /* One pre-split weight image: the B operand of a GEMM with N columns and reduction length K,

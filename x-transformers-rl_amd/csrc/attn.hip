@@ -14,6 +14,15 @@
 //     one block covers rows 4 (i >> 2) + 0..3 and columns j, j + 16, j + 32, j + 48 of a 64-key tile:
 //     exactly the 16 scores one lane holds in the forward and dQ kernels (one block per lane and tile)
 //   word mode: word (i & 3) of philox(seed; i >> 2, j, c2, FIELD_DROPOUT << 24 | sub) >= p 2^32.
+// Attention sinks (AttnProblem.mem_kv M learned memory key / value rows per kv head, zero_kv Z one all-zero
+// key / value): columns every row sees, folded into the online softmax before the key-tile loop — Z is the
+// initial state m = 0, l = 1, o = 0 and the memory rows are one 16-column sub-tile — so lse includes them
+// and the backward kernels of the real keys (which recompute P from lse and use D = rowsum(dO * O)) stay
+// as they are.  k_attn_sink_bwd adds the sink term of dQ and forms dmem_k / dmem_v.
+//   keep bit of memory column m at row i, in either mode: word (i & 3) of
+//     philox(seed; i >> 2, 0x80000000 | m, c2, c3) >= p 2^32, c3 the call's own (byte mode: its flag set).
+//   A real key's c1 is j or 16 (j >> 6) + (j & 15) with j < n < 2^31: no real key draws from a counter
+//   with bit 31 of c1 set, and the real keys' bits do not depend on M.  The zero key's value is 0: no bit.
 #include "kernels.h"
 #include "philox.h"
 
@@ -61,7 +70,13 @@ struct AttnArgs {
   // in layout kvgrad hold Hkv heads; query head h reads kv head kv_head_of(h, Hkv)
   int Hkv;
   AttnLayout kv, kvgrad;
+  // attention sinks (read by the SINK = true forward and by k_attn_sink_bwd / k_attn_sink_reduce only)
+  const float *MK, *MV;   // [Hkv][M][dh]
+  float *dMKp, *dMVp;     // per-(b, h) partials [b H][M][dh]
+  float *dMK, *dMV;       // [Hkv][M][dh]
+  int M, Z, dm_accum;
 };
+constexpr uint32_t SINK_C1 = 0x80000000u;   // c1 of a memory column's keep word: SINK_C1 | m
 constexpr int NO_WINDOW = 1 << 30;   // (i - j <= NO_WINDOW always holds; band tile ranges become the causal ones)
 
 // first row of episode b in layout L: b * sb (padded [b][n] tokens), or ep_off[b] rows (packed)
@@ -71,7 +86,9 @@ __device__ __forceinline__ int64_t ebase(const AttnArgs& a, const AttnLayout& L,
 
 // ---------------------------------------------------------------------------------------------
 // GQA = true (Hkv < H): the K / V base is the kv head's, in its own layout; nothing else changes
-template <int DH, bool GQA = false>
+// SINK = true (M + Z > 0): the sinks enter the softmax state before the key-tile loop (instantiations of
+// their own: the forms without sinks keep their code)
+template <int DH, bool GQA = false, bool SINK = false>
 __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Ks[TK][KST], Vs[TK][KST];
@@ -106,6 +123,52 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
 #pragma unroll
   for (int d = 0; d < ND; ++d) o[d] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
+  if constexpr (SINK) {
+    if (a.Z) {   // the zero key: score 0, value 0
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        m[r] = 0.f;
+        l[r] = 1.f;
+      }
+    }
+    if (a.M > 0) {   // the memory rows of this head's kv head: one 16-column sub-tile (columns >= M masked)
+      const float* mk = a.MK + (int64_t)kv_head_of(h, a.Hkv) * a.M * DH;
+      const float* mv = a.MV + (int64_t)kv_head_of(h, a.Hkv) * a.M * DH;
+      for (int x = tid; x < 16 * DH; x += 256) {
+        const int j = x / DH, c = x - j * DH;
+        Ks[j][c] = j < a.M ? mk[j * DH + c] : 0.f;
+        Vs[j][c] = j < a.M ? mv[j * DH + c] : 0.f;
+      }
+      __syncthreads();
+      f32x4v sacc = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < KS; ++s) sacc = mfma16(qa[s], Ks[lr][4 * s + lg], sacc);
+      u32x4_t kw = {};
+      if (a.thresh) kw = philox4x32_10((uint32_t)((q0 + 16 * w + 4 * lg) >> 2), SINK_C1 | (uint32_t)lr, off, a.c3, a.seed);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float sv = lr < a.M ? sacc[r] * a.scale : -INFINITY;
+        float mx = sv;
+#pragma unroll
+        for (int o2 = 1; o2 < 16; o2 <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o2, 64));
+        const float mnew = fmaxf(m[r], mx);
+        const float alpha = (m[r] == -INFINITY) ? 0.f : expf(m[r] - mnew);
+        const float p = (sv == -INFINITY) ? 0.f : expf(sv - mnew);
+        float rs = p;
+#pragma unroll
+        for (int o2 = 1; o2 < 16; o2 <<= 1) rs += __shfl_xor(rs, o2, 64);
+        Ps[w][4 * lg + r][lr] = (a.thresh && qword(kw, r) < a.thresh) ? 0.f : p * a.inv_keep;
+        l[r] = l[r] * alpha + rs;
+        m[r] = mnew;
+      }
+      wave_sync();
+#pragma unroll
+      for (int d = 0; d < ND; ++d)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) o[d] = mfma16(Ps[w][lr][4 * s + lg], Vs[4 * s + lg][16 * d + lr], o[d]);
+      wave_sync();
+    }
+  }
   const int last_key = min(min(a.causal ? q0 + TQ - 1 : n - 1, n - 1), len - 1);
   // the first key tile of the band: row q0's oldest visible key q0 - W.  A later row of the tile may
   // see nothing in it (its band starts in the next tile): it carries m = -inf, l = 0, o = 0 on
@@ -183,7 +246,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
       // a padded row (i >= len) whose whole band lies past the valid keys saw nothing: o = 0, lse = 0
       // here; k_attn_dead_fwd then stores its uniform average (no window: every row of an episode
       // with a valid key sees key 0)
-      const bool dead = a.window != NO_WINDOW && l[r] == 0.f;
+      const bool dead = !SINK && a.window != NO_WINDOW && l[r] == 0.f;   // (with a sink l >= its term > 0)
 #pragma unroll
       for (int d = 0; d < ND; ++d) {
         const int64_t at = ob + (int64_t)i * osi + 16 * d + lr;
@@ -809,8 +872,119 @@ __global__ __launch_bounds__(256) void k_attn_dead_bwd(const AttnArgs a) {
   if (len + a.window < n) a.dV[gb + (int64_t)j * gsi + c] += acc / (float)n;
 }
 
-// whether a problem can have such rows: a window, the padded layout, and a row n - 1 >= 1 + W
-bool has_dead_rows(const AttnProblem& p) { return p.window > 0 && !p.ep_off && p.window <= p.n - 2; }
+// ---------------------------------------------------------------------------------------------
+// Sink backward (M > 0), after the backward of the real keys on the same stream.  One workgroup per
+// (b, h) walks the head's rows in chunks of SB_ROWS, a thread per row:
+//   P_im = exp(scale q_i . mem_k[g, m] - lse_i), dS_im = P_im (z_im dO_i . mem_v[g, m] - D_i) with D_i =
+//   rowsum(dO_i * O_i) formed here (the order of k_attn_bwd_dkdv's sum), dq_i += scale sum_m dS_im mem_k[g, m]
+// and leaves dS and P~ = z P of the chunk in LDS; then thread (m, c) adds the chunk's rows, ascending,
+// into its elements of the head's partials  dmem_k[m][c] = scale sum_i dS_im q_i[c],  dmem_v[m][c] =
+// sum_i P~_im dO_i[c].  The rows are all the step holds: n (padded layout) or min(len, n) (packed).
+// k_attn_sink_reduce sums the partials over b and over a kv head's query heads in ascending order: no
+// atomics, the same bits every run.  (The zero key has no gradient of its own: it is in lse.)
+constexpr int SB_ROWS = 256, SB_ST = kMaxMemKV + 1;
+template <int DH>
+__global__ __launch_bounds__(256) void k_attn_sink_bwd(const AttnArgs a) {
+  constexpr int EU = kMaxMemKV * DH / 256;   // (m, c) elements per thread
+  __shared__ float mk[kMaxMemKV][DH], mv[kMaxMemKV][DH];
+  __shared__ float dSs[SB_ROWS][SB_ST], Pds[SB_ROWS][SB_ST];
+  const int tid = threadIdx.x;
+  const int bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H, ns = a.n;
+  const int len = a.lens[b];
+  const int n = a.ep_off ? min(len, ns) : ns;   // packed rows: the episode's own length
+  const int M = a.M;
+  const int64_t ib = ebase(a, a.in, b) + h * a.in.sh, ob = ebase(a, a.out, b) + h * a.out.sh, gb = ebase(a, a.grad, b) + h * a.grad.sh;
+  const int isi = a.in.si, osi = a.out.si, gsi = a.grad.si;
+  const uint32_t off = a.offset + (uint32_t)bh;
+  {
+    const int64_t mb = (int64_t)kv_head_of(h, a.Hkv) * M * DH;
+    for (int x = tid; x < M * DH; x += 256) {
+      mk[x / DH][x % DH] = a.MK[mb + x];
+      mv[x / DH][x % DH] = a.MV[mb + x];
+    }
+  }
+  float ak[EU], av[EU];
+#pragma unroll
+  for (int u = 0; u < EU; ++u) ak[u] = av[u] = 0.f;
+  for (int i0 = 0; i0 < n; i0 += SB_ROWS) {
+    __syncthreads();   // mk / mv staged; the chunk before is summed
+    const int i = i0 + tid;
+    if (i < n) {
+      float qr[DH], dor[DH], dq[DH];
+      float dsum = 0.f;
+#pragma unroll
+      for (int c = 0; c < DH; ++c) {
+        qr[c] = a.Q[ib + (int64_t)i * isi + c];
+        dor[c] = a.dO[ob + (int64_t)i * osi + c];
+        dq[c] = 0.f;
+      }
+#pragma unroll
+      for (int c = 0; c < DH; ++c) dsum += dor[c] * a.O[ob + (int64_t)i * osi + c];
+      const float lse = a.LSE[(int64_t)bh * ns + i];
+      for (int m = 0; m < M; ++m) {
+        float t = 0.f, gd = 0.f;
+#pragma unroll
+        for (int c = 0; c < DH; ++c) {
+          t += qr[c] * mk[m][c];
+          gd += dor[c] * mv[m][c];
+        }
+        const float p = expf(t * a.scale - lse);
+        float z = 1.f;
+        if (a.thresh) z = keep_word(a.seed, off, a.c3, i, (int)(SINK_C1 | (uint32_t)m)) >= a.thresh ? a.inv_keep : 0.f;
+        const float ds = p * (gd * z - dsum);
+        dSs[tid][m] = ds;
+        Pds[tid][m] = p * z;
+#pragma unroll
+        for (int c = 0; c < DH; ++c) dq[c] += ds * mk[m][c];
+      }
+#pragma unroll
+      for (int c = 0; c < DH; ++c) a.dQ[gb + (int64_t)i * gsi + c] += dq[c] * a.scale;
+    }
+    __syncthreads();
+    const int rows = min(SB_ROWS, n - i0);
+#pragma unroll
+    for (int u = 0; u < EU; ++u) {
+      const int e = tid + 256 * u, m = e / DH, c = e - m * DH;
+      if (m < M) {
+        for (int ii = 0; ii < rows; ++ii) {
+          ak[u] += dSs[ii][m] * a.Q[ib + (int64_t)(i0 + ii) * isi + c];
+          av[u] += Pds[ii][m] * a.dO[ob + (int64_t)(i0 + ii) * osi + c];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < EU; ++u) {
+    const int e = tid + 256 * u;
+    if (e < M * DH) {
+      a.dMKp[(int64_t)bh * M * DH + e] = ak[u] * a.scale;
+      a.dMVp[(int64_t)bh * M * DH + e] = av[u];
+    }
+  }
+}
+
+// dmem_k / dmem_v [Hkv][M][dh] = (dm_accum: +=) the partials summed over b, then over the kv head's query
+// heads, both ascending; thread per element
+__global__ __launch_bounds__(256) void k_attn_sink_reduce(const AttnArgs a, int B, int dh) {
+  const int x = blockIdx.x * 256 + threadIdx.x, per = a.M * dh;
+  if (x >= a.Hkv * per) return;
+  const int g = x / per, e = x - g * per;
+  float sk = 0.f, sv = 0.f;
+  for (int b = 0; b < B; ++b)
+    for (int h = 0; h < a.H; ++h) {
+      if (kv_head_of(h, a.Hkv) != g) continue;
+      sk += a.dMKp[(int64_t)(b * a.H + h) * per + e];
+      sv += a.dMVp[(int64_t)(b * a.H + h) * per + e];
+    }
+  a.dMK[x] = a.dm_accum ? a.dMK[x] + sk : sk;
+  a.dMV[x] = a.dm_accum ? a.dMV[x] + sv : sv;
+}
+
+// whether a problem can have such rows: a window, the padded layout, and a row n - 1 >= 1 + W — and no
+// sink (with one, a row without a visible key attends the sinks alone)
+bool has_dead_rows(const AttnProblem& p) {
+  return p.window > 0 && !p.ep_off && p.window <= p.n - 2 && !attn_has_sinks(p);
+}
 
 // grouped-query attention proper: fewer kv heads than query heads (Hkv = 0 or H: today's kernels)
 bool is_gqa(const AttnProblem& p) { return p.Hkv > 0 && p.Hkv < p.H; }
@@ -850,6 +1024,33 @@ int fill_args(AttnArgs& a, const AttnProblem& p) {
   a.Hkv = gqa ? p.Hkv : p.H;
   a.kv = gqa ? p.kv : p.in;
   a.kvgrad = gqa ? p.kvgrad : p.grad;
+  XTRL_REQUIRE(p.mem_kv >= 0 && p.mem_kv <= kMaxMemKV, "attn: num_mem_kv %d outside [0, %d]", p.mem_kv, kMaxMemKV);
+  XTRL_REQUIRE(p.mem_kv == 0 || (p.mem_k && p.mem_v), "attn: num_mem_kv %d without mem_k / mem_v", p.mem_kv);
+  XTRL_REQUIRE(!attn_has_sinks(p) || p.causal, "attn: the sinks need causal attention");
+  a.MK = p.mem_k;
+  a.MV = p.mem_v;
+  a.M = p.mem_kv;
+  a.Z = p.zero_kv ? 1 : 0;
+  return XTRL_OK;
+}
+
+// the sink part of the backward (M > 0), after the real keys' kernels: dQ += ..., dmem_k / dmem_v
+int sink_bwd(AttnArgs& a, const AttnProblem& p, hipStream_t s) {
+  if (p.mem_kv <= 0) return XTRL_OK;
+  XTRL_REQUIRE(p.dmem_k && p.dmem_v, "attn_bwd: num_mem_kv %d without dmem_k / dmem_v", p.mem_kv);
+  const int64_t need = attn_sink_ws_floats(p.b, p.H, p.mem_kv, p.dh);
+  XTRL_REQUIRE(p.sink_ws && p.sink_ws_floats >= need, "attn_bwd: sink workspace %lld < %lld floats",
+               (long long)p.sink_ws_floats, (long long)need);
+  a.dMKp = p.sink_ws;
+  a.dMVp = p.sink_ws + need / 2;
+  a.dMK = p.dmem_k;
+  a.dMV = p.dmem_v;
+  a.dm_accum = p.dmem_accum;
+  if (p.dh == 16) hipLaunchKernelGGL(k_attn_sink_bwd<16>, dim3(p.b * p.H), dim3(256), 0, s, a);
+  else if (p.dh == 32) hipLaunchKernelGGL(k_attn_sink_bwd<32>, dim3(p.b * p.H), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_attn_sink_bwd<64>, dim3(p.b * p.H), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_attn_sink_reduce, dim3((a.Hkv * p.mem_kv * p.dh + 255) / 256), dim3(256), 0, s, a, p.b, p.dh);
+  XTRL_LAUNCHED("attn_sink_bwd");
   return XTRL_OK;
 }
 
@@ -885,7 +1086,13 @@ int attn_fwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   a.OGout = og;
   const bool gqa = is_gqa(p);
   dim3 grid((p.n + TQ - 1) / TQ, p.b * p.H);
-  XTRL_ATTN_LAUNCH_DH(k_attn_fwd, gqa, p.dh, grid);
+  if (attn_has_sinks(p)) {   // the sink form (one per dh: it takes the kv head mapping at run time, Hkv = H included)
+    if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, true>), grid, dim3(256), 0, s, a);
+    else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_fwd<64, true, true>), grid, dim3(256), 0, s, a);
+  } else {
+    XTRL_ATTN_LAUNCH_DH(k_attn_fwd, gqa, p.dh, grid);
+  }
   XTRL_LAUNCHED("attn_fwd");
   if (has_dead_rows(p)) {
     dim3 dgrid((p.n + 256 / p.dh - 1) / (256 / p.dh), p.b * p.H);
@@ -959,12 +1166,15 @@ int attn_bwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
     XTRL_ATTN_LAUNCH_DH(k_attn_dead_bwd, gqa, p.dh, dgrid);
     XTRL_LAUNCHED("attn_dead_bwd");
   }
-  return XTRL_OK;
+  return sink_bwd(a, p, s);
 }
 
 int64_t attn_dq_part_floats(int b, int H, int n, int dh) {
   return (int64_t)((n + TK - 1) / TK) * b * H * n * dh;
 }
+
+// per-(b, h) partials of dmem_k and of dmem_v
+int64_t attn_sink_ws_floats(int b, int H, int mem_kv, int dh) { return 2 * (int64_t)b * H * mem_kv * dh; }
 
 AttnProblem contiguous_problem(const int32_t* lens, int b, int H, int n, int dh, float scale, float p, uint64_t seed,
                                uint32_t offset, uint32_t sub, int window, int Hkv) {
@@ -979,12 +1189,24 @@ AttnProblem contiguous_problem(const int32_t* lens, int b, int H, int n, int dh,
 
 }  // namespace xtrl
 
+extern "C" int xtrl_attn_fwd_sink(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
+                                  float* lse, const float* mem_k, const float* mem_v, int b, int H, int Hkv, int n,
+                                  int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
+                                  int window, int num_mem_kv, int add_zero_kv, void* stream) {
+  XTRL_REQUIRE(Hkv >= 1, "attn_fwd: kv heads %d < 1", Hkv);
+  xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv);
+  pr.mem_k = mem_k;
+  pr.mem_v = mem_v;
+  pr.mem_kv = num_mem_kv;
+  pr.zero_kv = add_zero_kv;
+  return xtrl::attn_fwd_ex(pr, q, k, v, o, lse, nullptr, nullptr, xtrl::as_stream(stream));
+}
+
 extern "C" int xtrl_attn_fwd_gqa(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
                                  float* lse, int b, int H, int Hkv, int n, int dh, float scale, float dropout_p,
                                  uint64_t seed, uint32_t offset, uint32_t sub, int window, void* stream) {
-  XTRL_REQUIRE(Hkv >= 1, "attn_fwd_gqa: kv heads %d < 1", Hkv);
-  return xtrl::attn_fwd_ex(xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv),
-                           q, k, v, o, lse, nullptr, nullptr, xtrl::as_stream(stream));
+  return xtrl_attn_fwd_sink(q, k, v, lens, o, lse, nullptr, nullptr, b, H, Hkv, n, dh, scale, dropout_p, seed, offset,
+                            sub, window, 0, 0, stream);
 }
 
 extern "C" int xtrl_attn_fwd_win(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
@@ -1003,16 +1225,51 @@ extern "C" int64_t xtrl_attn_bwd_part_floats(int b, int H, int n, int dh) {
   return xtrl::attn_dq_part_floats(b, H, n, dh);
 }
 
+extern "C" int64_t xtrl_attn_sink_ws_floats(int b, int H, int num_mem_kv, int dh) {
+  return xtrl::attn_sink_ws_floats(b, H, num_mem_kv, dh);
+}
+
+extern "C" int xtrl_attn_bwd_part_sink(const float* q, const float* k, const float* v, const int32_t* lens,
+                                       const float* o, const float* lse, const float* dout, float* dq, float* dk,
+                                       float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats,
+                                       const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v,
+                                       float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh,
+                                       float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
+                                       int window, int num_mem_kv, int add_zero_kv, void* stream) {
+  XTRL_REQUIRE(Hkv >= 1, "attn_bwd: kv heads %d < 1", Hkv);
+  xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv);
+  pr.dq_part = dq_part;
+  pr.dq_part_floats = dq_part_floats;
+  pr.mem_k = mem_k;
+  pr.mem_v = mem_v;
+  pr.mem_kv = num_mem_kv;
+  pr.zero_kv = add_zero_kv;
+  pr.dmem_k = dmem_k;
+  pr.dmem_v = dmem_v;
+  pr.sink_ws = sink_ws;
+  pr.sink_ws_floats = sink_ws_floats;
+  return xtrl::attn_bwd_ex(pr, q, k, v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+}
+
+extern "C" int xtrl_attn_bwd_sink(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                                  const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                                  const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v, float* sink_ws,
+                                  int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh, float scale,
+                                  float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, int window,
+                                  int num_mem_kv, int add_zero_kv, void* stream) {
+  return xtrl_attn_bwd_part_sink(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, nullptr, 0, mem_k, mem_v, dmem_k,
+                                 dmem_v, sink_ws, sink_ws_floats, b, H, Hkv, n, dh, scale, dropout_p, seed, offset, sub,
+                                 window, num_mem_kv, add_zero_kv, stream);
+}
+
 extern "C" int xtrl_attn_bwd_part_gqa(const float* q, const float* k, const float* v, const int32_t* lens,
                                       const float* o, const float* lse, const float* dout, float* dq, float* dk,
                                       float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats, int b, int H,
                                       int Hkv, int n, int dh, float scale, float dropout_p, uint64_t seed,
                                       uint32_t offset, uint32_t sub, int window, void* stream) {
-  XTRL_REQUIRE(Hkv >= 1, "attn_bwd_part_gqa: kv heads %d < 1", Hkv);
-  xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv);
-  pr.dq_part = dq_part;
-  pr.dq_part_floats = dq_part_floats;
-  return xtrl::attn_bwd_ex(pr, q, k, v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+  return xtrl_attn_bwd_part_sink(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, dq_part, dq_part_floats, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, 0, b, H, Hkv, n, dh, scale, dropout_p, seed,
+                                 offset, sub, window, 0, 0, stream);
 }
 
 extern "C" int xtrl_attn_bwd_part_win(const float* q, const float* k, const float* v, const int32_t* lens,
@@ -1036,9 +1293,8 @@ extern "C" int xtrl_attn_bwd_gqa(const float* q, const float* k, const float* v,
                                  const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
                                  int b, int H, int Hkv, int n, int dh, float scale, float dropout_p, uint64_t seed,
                                  uint32_t offset, uint32_t sub, int window, void* stream) {
-  XTRL_REQUIRE(Hkv >= 1, "attn_bwd_gqa: kv heads %d < 1", Hkv);
-  return xtrl::attn_bwd_ex(xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv),
-                           q, k, v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+  return xtrl_attn_bwd_sink(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, 0, b, H, Hkv, n, dh, scale, dropout_p, seed, offset, sub, window, 0, 0, stream);
 }
 
 extern "C" int xtrl_attn_bwd_win(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,

@@ -332,7 +332,40 @@ struct FrPost {
   float eps = 1e-5f;
 };
 
-template <int DH, int FJ>
+// Attention sinks (SINK = true, D.num_mem_kv + D.add_zero_kv > 0; instantiations of their own): the M memory
+// rows of the kv head (Ly.mem_k / mem_v [Hkv][M][dh], no rotary) and the zero key enter the softmax
+// after the cached keys — lane m holds memory row m's score, taken from the layer's weights once the
+// cache prefetch is out; the maximum, the sum and the unnormalised P.V are rescaled once at the end —
+// so the cache loops, the prefetch and the window's pointer shift are those of the form without sinks
+template <int DH>
+__device__ __forceinline__ float sink_score(const float* mem_k, int kvh, int M, int lane, const float* q, float scale) {
+  float s = 0.f;
+  if (lane < M) {
+    const float4* mkr = reinterpret_cast<const float4*>(mem_k + ((int64_t)kvh * M + lane) * DH);
+#pragma unroll
+    for (int i = 0; i < DH / 4; ++i) {
+      const float4 kv = mkr[i];
+      s += q[4 * i] * kv.x;
+      s += q[4 * i + 1] * kv.y;
+      s += q[4 * i + 2] * kv.z;
+      s += q[4 * i + 3] * kv.w;
+    }
+  }
+  return lane < M ? s * scale : -INFINITY;
+}
+// folds the sinks into (mx, sum): returns the factor for the terms formed against the old maximum and,
+// in ps, this lane's memory row's probability (against the new one)
+__device__ __forceinline__ float sink_fold(float ts, int zero_kv, float& mx, float& sum, float& ps) {
+  float mx2 = fmaxf(mx, wave_max_dpp(ts));
+  if (zero_kv) mx2 = fmaxf(mx2, 0.f);
+  const float f = expf(mx - mx2);
+  ps = ts == -INFINITY ? 0.f : expf(ts - mx2);
+  sum = sum * f + wave_sum_dpp(ps) + (zero_kv ? expf(-mx2) : 0.f);
+  mx = mx2;
+  return f;
+}
+
+template <int DH, int FJ, bool SINK = false>
 __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDecodeDesc D, const XtrlDecodeLayer Ly, int layer,
                                                       int t, const FrPost fp) {
   constexpr int CK = DH <= 32 ? 128 : 64;          // keys per chunk
@@ -447,6 +480,8 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
   float qreg[DH];
 #pragma unroll
   for (int i = 0; i < DH; ++i) qreg[i] = qs[i];
+  float ts = -INFINITY;   // SINK: memory row `lane`'s score
+  if constexpr (SINK) ts = sink_score<DH>(Ly.mem_k, kvh, D.num_mem_kv, lane, qreg, scale);
   // scores, one key per lane; chunk 0 from the prefetched rows
   float mx = -INFINITY;
   for (int j0 = 0; j0 <= tw; j0 += CK) {
@@ -525,6 +560,19 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
   acc.y = kpi_sum<KPI>(acc.y);
   acc.z = kpi_sum<KPI>(acc.z);
   acc.w = kpi_sum<KPI>(acc.w);
+  if constexpr (SINK) {
+    float ps;
+    const float f = sink_fold(ts, D.add_zero_kv, mx, sum, ps);
+    acc = make_float4(acc.x * f, acc.y * f, acc.z * f, acc.w * f);
+    for (int m = 0; m < D.num_mem_kv; ++m) {
+      const float pm = __shfl(ps, m, 64);
+      const float4 v4 = *reinterpret_cast<const float4*>(Ly.mem_v + ((int64_t)kvh * D.num_mem_kv + m) * DH + 4 * cq);
+      acc.x += pm * v4.x;
+      acc.y += pm * v4.y;
+      acc.z += pm * v4.z;
+      acc.w += pm * v4.w;
+    }
+  }
   if (kk == 0) {
     float o4[4] = {acc.x / sum, acc.y / sum, acc.z / sum, acc.w / sum};
     if (D.gate_values) {
@@ -977,6 +1025,11 @@ int check_desc(const XtrlDecodeDesc* D) {
                "decode: n_qkv mismatch (I + 2 Ikv (+ I gate) (+ Hkv mix))");
   XTRL_REQUIRE(!D->ff_glu || (D->hglu && D->hff), "decode: ff_glu needs hglu");
   XTRL_REQUIRE(D->attn_window >= 0, "decode: attn_window %d < 0 (0 = no window)", D->attn_window);
+  XTRL_REQUIRE(D->num_mem_kv >= 0 && D->num_mem_kv <= kMaxMemKV, "decode: num_mem_kv %d outside [0, %d]", D->num_mem_kv,
+               kMaxMemKV);
+  for (int l = 0; l < D->L && D->num_mem_kv > 0; ++l)
+    XTRL_REQUIRE(D->layers[l].mem_k && D->layers[l].mem_v, "decode: layer %d num_mem_kv %d without mem_k / mem_v", l,
+                 D->num_mem_kv);
   return XTRL_OK;
 }
 
@@ -1403,10 +1456,13 @@ int launch_mlp(const XtrlDecodeDesc* D, int l, int t, hipStream_t s) {
 }
 
 int launch_attn_decode(const XtrlDecodeDesc* D, int l, int t, hipStream_t s, const FrPost& fp = FrPost{}) {
+  const bool sinks = D->num_mem_kv > 0 || D->add_zero_kv;   // the SINK forms (checked by check_desc)
   if (attn_fused(D, l)) {   // one workgroup of H waves per live row
     const size_t lds = ((size_t)D->H * (D->Tmax + 3 * D->dh) + (size_t)D->H * D->d) * sizeof(float);
     const dim3 grid(D->E), blk(64 * D->H);
-    if (D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    if (sinks && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    else if (sinks) hipLaunchKernelGGL((k_attn_decode<16, 1, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    else if (D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
     else hipLaunchKernelGGL((k_attn_decode<16, 1>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
     XTRL_LAUNCHED("attn_decode");
     return XTRL_OK;
@@ -1415,7 +1471,11 @@ int launch_attn_decode(const XtrlDecodeDesc* D, int l, int t, hipStream_t s, con
   const size_t lds = 4 * (size_t)(D->Tmax + 3 * D->dh) * sizeof(float);
   XTRL_REQUIRE(lds <= 160 * 1024, "attn_decode: Tmax %d too large for LDS", D->Tmax);
   dim3 grid((waves + 3) / 4);
-  if (D->dh == 16)
+  if (sinks) {
+    if (D->dh == 16) hipLaunchKernelGGL((k_attn_decode<16, 0, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
+    else if (D->dh == 32) hipLaunchKernelGGL((k_attn_decode<32, 0, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
+    else hipLaunchKernelGGL((k_attn_decode<64, 0, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
+  } else if (D->dh == 16)
     hipLaunchKernelGGL((k_attn_decode<16, 0>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
   else if (D->dh == 32)
     hipLaunchKernelGGL((k_attn_decode<32, 0>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
@@ -1861,7 +1921,8 @@ constexpr uint32_t HG_CANCEL = 0xFFFFFFFFu;
 // takes 4 d / Ge of the heads' hidden units and its partial of the last Linear; the partials meet
 // through k_mlp's hand-off (sc1 stores, one counter per row) and the last arriver sums them in
 // workgroup order, adds b2 and samples.  The heads are ~40 % of a row's weight bytes (C2).
-template <int DH, int KP = (DH == 16 ? 2 : 1)>   // KP: 64-key K passes per round trip
+// SINK: attention sinks, as k_attn_decode<., ., true>
+template <int DH, int KP = (DH == 16 ? 2 : 1), bool SINK = false>   // KP: 64-key K passes per round trip
 __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, int t, int G, const HostGate hg) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ int rows_sh[EMB_MAX_E];
@@ -2141,10 +2202,32 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
         acc.y = kpi_sum<KPI>(acc.y);
         acc.z = kpi_sum<KPI>(acc.z);
         acc.w = kpi_sum<KPI>(acc.w);
+        float fs = 1.f;
+        float4 sk4 = make_float4(0.f, 0.f, 0.f, 0.f);   // SINK: the memory rows' P.V, the factor of the other terms
+        if constexpr (SINK) {
+          const float ts = sink_score<DH>(Ly.mem_k, kvh, D.num_mem_kv, lane, att + h * DH, scale);
+          float ps;
+          fs = sink_fold(ts, D.add_zero_kv, mx, sum, ps);
+          for (int m = 0; m < D.num_mem_kv; ++m) {
+            const float pm = __shfl(ps, m, 64);
+            const float4 v4 = *reinterpret_cast<const float4*>(Ly.mem_v + ((int64_t)kvh * D.num_mem_kv + m) * DH + 4 * cq);
+            sk4.x += pm * v4.x;
+            sk4.y += pm * v4.y;
+            sk4.z += pm * v4.z;
+            sk4.w += pm * v4.w;
+          }
+          wave_sync();   // (every lane has read q from the head's att slot before it takes the output)
+        }
         if (kk == 0) {   // + the new key's term, normalise, gate
           const float* vn = sc + round4i(D.Tmax) + 4 * cq;
           float o4[4] = {(acc.x + pn * vn[0]) / sum, (acc.y + pn * vn[1]) / sum, (acc.z + pn * vn[2]) / sum,
                          (acc.w + pn * vn[3]) / sum};
+          if constexpr (SINK) {
+            o4[0] = ((acc.x + pn * vn[0]) * fs + sk4.x) / sum;
+            o4[1] = ((acc.y + pn * vn[1]) * fs + sk4.y) / sum;
+            o4[2] = ((acc.z + pn * vn[2]) * fs + sk4.z) / sum;
+            o4[3] = ((acc.w + pn * vn[3]) * fs + sk4.w) / sum;
+          }
           if (D.gate_values) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) o4[i] *= sigmoidf_(qkv[I + 2 * Ikv + h * DH + 4 * cq + i]);
@@ -2302,7 +2385,11 @@ int decode_step_rows(const XtrlDecodeDesc* D, int t, int max_rows, hipStream_t s
   const size_t lds = (size_t)row_lds(*D).tot * sizeof(float);
   if (hg.go) XTRL_REQUIRE(grid.x == 1 && D->act_host, "decode rows: the gated host step takes one row (E == 1) "
                                                        "and the pinned action buffer");
-  if (D->dh == 16) hipLaunchKernelGGL(k_decode_row<16>, grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+  if (D->num_mem_kv > 0 || D->add_zero_kv) {   // the SINK forms
+    if (D->dh == 16) hipLaunchKernelGGL((k_decode_row<16, 2, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+    else if (D->dh == 32) hipLaunchKernelGGL((k_decode_row<32, 1, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+    else hipLaunchKernelGGL((k_decode_row<64, 1, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+  } else if (D->dh == 16) hipLaunchKernelGGL(k_decode_row<16>, grid, dim3(ROW_T), lds, s, *D, t, G, hg);
   else if (D->dh == 32) hipLaunchKernelGGL(k_decode_row<32>, grid, dim3(ROW_T), lds, s, *D, t, G, hg);
   else hipLaunchKernelGGL(k_decode_row<64>, grid, dim3(ROW_T), lds, s, *D, t, G, hg);
   XTRL_LAUNCHED("decode_row");

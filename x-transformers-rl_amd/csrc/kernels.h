@@ -233,7 +233,22 @@ struct AttnProblem {
   // with `kv` and dk, dv with `kvgrad` (q and dq keep `in` and `grad`)
   int Hkv = 0;
   AttnLayout kv = {}, kvgrad = {};
+  // attention sinks (x-transformers attn_num_mem_kv / attn_add_zero_kv): mem_kv learned memory key / value
+  // rows [Hkv][mem_kv][dh] (mem_kv <= kMaxMemKV) and, with zero_kv, one all-zero key / value, visible to
+  // every query row whatever the causal, padding or window mask says (no rotary, not counted in the
+  // window).  A row without a visible real key attends the sinks alone, so the uniform dead-row rule of
+  // the window does not apply.  Backward: dmem_k / dmem_v [Hkv][mem_kv][dh] (dmem_accum: added to, else
+  // stored) via per-(b, h) partials in sink_ws (attn_sink_ws_floats), summed in a fixed order
+  const float *mem_k = nullptr, *mem_v = nullptr;
+  int mem_kv = 0, zero_kv = 0;
+  float *dmem_k = nullptr, *dmem_v = nullptr;
+  int dmem_accum = 0;
+  float* sink_ws = nullptr;
+  int64_t sink_ws_floats = 0;
 };
+constexpr int kMaxMemKV = 16;   // one 16-column MFMA sub-tile
+inline bool attn_has_sinks(const AttnProblem& p) { return p.mem_kv > 0 || p.zero_kv != 0; }
+int64_t attn_sink_ws_floats(int b, int H, int mem_kv, int dh);
 // the kv head that query head h reads: x-transformers repeats k / v as 'b kvh n d -> b (r kvh) n d', so
 // the repeated head r * Hkv + kvh is kv head kvh.  The one place on the device side that knows the mapping
 __host__ __device__ inline int kv_head_of(int h, int Hkv) { return h % Hkv; }

@@ -1179,6 +1179,20 @@ AttnProblem attn_problem(const Ctx& c, const XtrlTrainLayer& Ly, int li) {
   p.Hkv = kv_heads(D);
   p.kv = p.in;
   p.kvgrad = p.grad;
+  // attention sinks: the memory keys / values are parameters of the flat buffer, their gradients go to the
+  // same offsets of the gradient buffer (accumulated, like every weight gradient), on the main stream
+  // before the layer's bucket is recorded
+  p.mem_kv = D->num_mem_kv;
+  p.zero_kv = D->add_zero_kv;
+  if (D->num_mem_kv > 0) {
+    p.mem_k = c.P(Ly.mem_k);
+    p.mem_v = c.P(Ly.mem_v);
+    p.dmem_k = c.G(Ly.mem_k);
+    p.dmem_v = c.G(Ly.mem_v);
+    p.dmem_accum = 1;
+    p.sink_ws = D->sink_ws;
+    p.sink_ws_floats = D->sink_ws_floats;
+  }
   return p;
 }
 
@@ -1189,6 +1203,11 @@ int validate(const XtrlTrainDesc* D) {
   XTRL_REQUIRE(D->dh % 2 == 0 && D->rot_dim <= D->dh, "train: bad rotary dims");
   XTRL_REQUIRE(D->Hkv >= 0 && D->Hkv <= D->H && D->H % kv_heads(D) == 0, "train: Hkv %d must divide H %d (0 = H)", D->Hkv,
                D->H);
+  XTRL_REQUIRE(D->num_mem_kv >= 0 && D->num_mem_kv <= kMaxMemKV, "train: num_mem_kv %d outside [0, %d]", D->num_mem_kv,
+               kMaxMemKV);
+  for (int li = 0; li < D->L; ++li)
+    XTRL_REQUIRE(D->num_mem_kv == 0 || (D->layers[li].mem_k >= 0 && D->layers[li].mem_v >= 0 && D->sink_ws),
+                 "train: layer %d num_mem_kv %d without mem_k / mem_v offsets or the sink workspace", li, D->num_mem_kv);
   for (int li = 0; li < D->L; ++li)
     XTRL_REQUIRE(D->layers[li].n_qkv == D->H * D->dh + 2 * kv_inner(D) + (D->gate_values ? D->H * D->dh : 0) +
                                             (D->layers[li].mix ? kv_heads(D) : 0),

@@ -64,6 +64,9 @@ XT_DEFAULTS = dict(
     attn_rotary_embed_values=False, attn_max_attend_past=None)
 
 
+MAX_MEM_KV = 16   # attn_num_mem_kv: the memory rows are one 16-column MFMA sub-tile (kernels.h kMaxMemKV)
+
+
 def epoch_permutation(seed, update, epoch, n):
     g = torch.Generator().manual_seed((int(seed) * 1000003 + int(update)) * 1000003 + int(epoch) & (2 ** 62 - 1))
     return torch.randperm(n, generator=g)
@@ -127,7 +130,7 @@ class Agent(nn.Module):
         known = {'attn_dim_head', 'heads', 'depth', 'attn_gate_values', 'add_value_residual',
                  'learned_value_residual_mix', 'ff_mult', 'ff_no_bias', 'ff_glu', 'attn_qk_norm',
                  'attn_qk_norm_scale', 'rotary_xpos', 'rotary_xpos_scale_base', 'use_rmsnorm',
-                 'attn_max_attend_past', 'attn_one_kv_head'}
+                 'attn_max_attend_past', 'attn_one_kv_head', 'attn_num_mem_kv', 'attn_add_zero_kv'}
         unknown = set(wm) - known
         if unknown:
             # (world_model['attn_kv_heads'] stays among the refused options, as before grouped-query attention
@@ -156,6 +159,20 @@ class Agent(nn.Module):
             raise ValueError(f'kv_heads must be an int from 1 to heads = {heads} that divides heads, or None, '
                              f'not {kv_heads!r}')
         kv_heads = 0 if kv_heads is None or kv_heads == heads else int(kv_heads)   # 0: plain multi-head attention
+        # attention sinks (x-transformers Attention num_mem_kv / add_zero_kv): learned memory key / value rows
+        # per kv head and / or one all-zero key / value, visible to every query whatever the masks say
+        num_mem_kv = wm.get('attn_num_mem_kv', 0)
+        if isinstance(num_mem_kv, bool) or not isinstance(num_mem_kv, (int, np.integer)) or \
+                not 0 <= num_mem_kv <= MAX_MEM_KV:
+            raise ValueError(f'attn_num_mem_kv must be an int from 0 to {MAX_MEM_KV} (one 16-column MFMA sub-tile), '
+                             f'not {num_mem_kv!r}')
+        add_zero_kv = wm.get('attn_add_zero_kv', False)
+        if not isinstance(add_zero_kv, (bool, np.bool_)):
+            raise ValueError(f'attn_add_zero_kv must be a bool, not {add_zero_kv!r}')
+        if num_mem_kv > 0 and wm.get('attn_qk_norm', False):
+            raise NotImplementedError('attn_num_mem_kv > 0 together with attn_qk_norm is not supported: x-transformers '
+                                      'normalises and rescales the memory keys there (attn_add_zero_kv with '
+                                      'attn_qk_norm is fine)')
         self.seed = int(seed)
         self.evolutionary = evolutionary
         self.evolve_every, self.evolve_after_step = evolve_every, evolve_after_step
@@ -174,6 +191,7 @@ class Agent(nn.Module):
                         rotary_xpos=bool(wm.get('rotary_xpos', False)),
                         xpos_scale_base=float(wm.get('rotary_xpos_scale_base', 512.)),
                         rotary_abs_rollout=rotary_abs_rollout, attn_window=int(window or 0), kv_heads=kv_heads,
+                        num_mem_kv=int(num_mem_kv), add_zero_kv=bool(add_zero_kv),
                         hl_reduction_mean=hl_reduction_mean, hl_sigma_ratio=hl_sigma_ratio)
         self.cfg = c
         # the learn step without the minibatch's padding (XtrlTrainDesc.packed): exact only with the
@@ -191,6 +209,9 @@ class Agent(nn.Module):
             if c.kv_heads:
                 raise NotImplementedError('the fractal policy body has no grouped-query attention: leave kv_heads / '
                                           'attn_one_kv_head unset (or kv_heads = heads)')
+            if c.num_mem_kv or c.add_zero_kv:
+                raise NotImplementedError('the fractal policy body has no attention sinks: leave attn_num_mem_kv at 0 '
+                                          'and attn_add_zero_kv at False')
             if c.gate_values or c.value_residual or c.ff_no_bias or c.ff_glu or c.qk_norm or c.rotary_xpos or c.rms_norm:
                 raise NotImplementedError('the fractal policy body has no gated values / value residual / bias-free or '
                                           'GLU feed-forward / qk norm / xPos rotary / RMSNorm: set attn_gate_values / '

@@ -54,6 +54,8 @@ class ModelConfig:
     xpos_scale_base: float = 512.        # x-transformers rotary_xpos_scale_base
     attn_window: int = 0                 # x-transformers attn_max_attend_past: key j visible iff 0 <= i - j <= W (0: none)
     kv_heads: int = 0                    # kv heads (GQA: Agent kv_heads / attn_one_kv_head); 0 or heads: multi-head
+    num_mem_kv: int = 0                  # x-transformers attn_num_mem_kv: learned memory key / value rows per kv head
+    add_zero_kv: bool = False            # x-transformers attn_add_zero_kv: one all-zero key / value ("+ 1" softmax)
     rotary_abs_rollout: bool = False     # decision log: reference semantics = rotary position 0 in rollout
     hl_reduction_mean: bool = True       # decision log: hl-gauss-pytorch default reduction
     hl_sigma_ratio: float = 2.0
@@ -122,6 +124,11 @@ class XAttention(nn.Module):
             self.to_value_residual_mix = nn.Sequential(nn.Linear(d, c.n_kv_heads))   # one mix per kv head
             nn.init.zeros_(self.to_value_residual_mix[0].weight)
             nn.init.zeros_(self.to_value_residual_mix[0].bias)
+        # attention sinks (x-transformers Attention num_mem_kv): memory keys / values every query sees, one
+        # set per kv head; no rotary, no value-residual mix (state-dict names mem_k / mem_v beside to_q)
+        if c.num_mem_kv > 0:
+            self.mem_k = nn.Parameter(torch.randn(c.n_kv_heads, c.num_mem_kv, c.dim_head))
+            self.mem_v = nn.Parameter(torch.randn(c.n_kv_heads, c.num_mem_kv, c.dim_head))
 
 
 class XGLU(nn.Module):
@@ -368,7 +375,9 @@ class WorldModelActorCritic(nn.Module):
                 q, k = F.normalize(q, dim=-1), F.normalize(k, dim=-1)
             q = torch.cat((q[..., :rot] * cos * xq + _rotate_half(q[..., :rot]) * sin * xq, q[..., rot:]), dim=-1)
             k = torch.cat((k[..., :rot] * cos * xk + _rotate_half(k[..., :rot]) * sin * xk, k[..., rot:]), dim=-1)
-            o = ops.attention(q, k, v, lens, scale, p_drop, attn_seed, attn_offset, li, window=c.attn_window)
+            o = ops.attention(q, k, v, lens, scale, p_drop, attn_seed, attn_offset, li, window=c.attn_window,
+                              mem_k=getattr(blk, 'mem_k', None), mem_v=getattr(blk, 'mem_v', None),
+                              add_zero_kv=c.add_zero_kv)
             o = o.permute(0, 2, 1, 3).reshape(b, n, I)
             if gate_pre is not None:
                 o = o * gate_pre.sigmoid()

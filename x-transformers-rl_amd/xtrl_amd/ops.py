@@ -219,10 +219,13 @@ def kv_head_index(heads, kv_heads, device=None):
 class AttentionFn(torch.autograd.Function):
     """softmax(q k^T * scale + causal/key-padding mask) with post-softmax dropout, times v.  q is
     [b][H][n][dh]; k, v are [b][Hkv][n][dh] with Hkv dividing H (grouped-query attention: query head h
-    reads kv head kv_head_index(H, Hkv)[h]; dk, dv come back [b][Hkv][n][dh], summed over each group)."""
+    reads kv head kv_head_index(H, Hkv)[h]; dk, dv come back [b][Hkv][n][dh], summed over each group).
+    Attention sinks: mem_k, mem_v [Hkv][M][dh] (or None) and add_zero_kv join every row's softmax
+    (include/xtrl_hip.h, xtrl_attn_fwd_sink); their gradients come back with dq, dk, dv."""
 
     @staticmethod
-    def forward(ctx, q, k, v, lens, scale, dropout_p, seed, offset, sub, window=0):
+    def forward(ctx, q, k, v, lens, scale, dropout_p, seed, offset, sub, window=0, mem_k=None, mem_v=None,
+                add_zero_kv=False):
         lib = L.lib()
         b, H, n, dh = q.shape
         Hkv = k.shape[1]
@@ -231,36 +234,58 @@ class AttentionFn(torch.autograd.Function):
             _f32c(t)
             assert t.shape == (b, heads, n, dh)
         assert lens.dtype == torch.int32 and lens.shape == (b,)
+        assert (mem_k is None) == (mem_v is None), 'mem_k and mem_v go together'
+        M = 0 if mem_k is None else mem_k.shape[1]
+        for t in (mem_k, mem_v):
+            if t is not None:
+                _f32c(t)
+                assert t.shape == (Hkv, M, dh), f'memory key / values must be [Hkv][M][dh], not {tuple(t.shape)}'
         o = torch.empty_like(q)
         lse = torch.empty(b, H, n, device=q.device, dtype=torch.float32)
-        L.check(lib.xtrl_attn_fwd_gqa(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), b, H, Hkv, n, dh,
-                                      float(scale), float(dropout_p), int(seed), int(offset), int(sub), int(window),
-                                      L.stream()), 'attn_fwd')
-        ctx.save_for_backward(q, k, v, lens, o, lse)
-        ctx.cfg = (float(scale), float(dropout_p), int(seed), int(offset), int(sub), int(window))
+        L.check(lib.xtrl_attn_fwd_sink(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse),
+                                       L.ptr(mem_k) if M else None, L.ptr(mem_v) if M else None, b, H, Hkv, n, dh,
+                                       float(scale), float(dropout_p), int(seed), int(offset), int(sub), int(window),
+                                       M, int(bool(add_zero_kv)), L.stream()), 'attn_fwd')
+        ctx.save_for_backward(q, k, v, lens, o, lse, *((mem_k, mem_v) if M else ()))
+        ctx.cfg = (float(scale), float(dropout_p), int(seed), int(offset), int(sub), int(window), M,
+                   int(bool(add_zero_kv)))
         return o
 
     @staticmethod
     def backward(ctx, do):
         lib = L.lib()
-        q, k, v, lens, o, lse = ctx.saved_tensors
-        scale, p, seed, offset, sub, window = ctx.cfg
+        q, k, v, lens, o, lse = ctx.saved_tensors[:6]
+        scale, p, seed, offset, sub, window, M, Z = ctx.cfg
+        mem_k, mem_v = ctx.saved_tensors[6:] if M else (None, None)
         b, H, n, dh = q.shape
         do = do.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         delta = torch.empty(b, H, n, device=q.device, dtype=torch.float32)
-        L.check(lib.xtrl_attn_bwd_gqa(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do),
-                                      L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(delta), b, H, k.shape[1], n, dh, scale, p,
-                                      seed, offset, sub, window, L.stream()), 'attn_bwd')
-        return dq, dk, dv, None, None, None, None, None, None, None
+        dmk = dmv = ws = None
+        ws_floats = 0
+        if M:
+            dmk, dmv = torch.empty_like(mem_k), torch.empty_like(mem_v)
+            ws_floats = int(lib.xtrl_attn_sink_ws_floats(b, H, M, dh))
+            ws = torch.empty(ws_floats, device=q.device, dtype=torch.float32)
+        pm = lambda t: L.ptr(t) if t is not None else None
+        L.check(lib.xtrl_attn_bwd_sink(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do),
+                                       L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(delta), pm(mem_k), pm(mem_v), pm(dmk),
+                                       pm(dmv), pm(ws), ws_floats, b, H, k.shape[1], n, dh, scale, p, seed, offset, sub,
+                                       window, M, Z, L.stream()), 'attn_bwd')
+        return dq, dk, dv, None, None, None, None, None, None, None, dmk, dmv, None
 
 
-def attention(q, k, v, lens, scale, dropout_p=0., seed=0, offset=0, sub=0, window=0):
+def attention(q, k, v, lens, scale, dropout_p=0., seed=0, offset=0, sub=0, window=0, mem_k=None, mem_v=None,
+              add_zero_kv=False):
     """``offset`` / ``sub``: the dropout stream (Philox c2 base and c3 sub-index = decoder layer);
     ``window`` > 0: query i sees key j only if i - j <= window (x-transformers max_attend_past).
-    k, v with fewer heads than q (a divisor): grouped-query attention (x-transformers attn_kv_heads)."""
+    k, v with fewer heads than q (a divisor): grouped-query attention (x-transformers attn_kv_heads).
+    ``mem_k`` / ``mem_v`` [Hkv][M][dh] and ``add_zero_kv``: attention sinks every row sees (x-transformers
+    attn_num_mem_kv / attn_add_zero_kv)."""
+    if mem_k is not None:
+        mem_k, mem_v = mem_k.contiguous(), mem_v.contiguous()
     return AttentionFn.apply(q.contiguous(), k.contiguous(), v.contiguous(), lens, scale, dropout_p, seed, offset,
-                             sub, window)
+                             sub, window, mem_k, mem_v, add_zero_kv)
 
 
 # --------------------------------------------------------------------------------------------

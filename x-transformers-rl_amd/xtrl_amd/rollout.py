@@ -122,6 +122,11 @@ class RolloutEngine:
         if self.rows_max:   # k-major copies for the row-resident step
             for wl in self.wl:
                 wl.update(w_qkv_t=z(d, _r4(self.n_qkv)), w_ff1_t=z(d, ff), w_ff2_t=z(ff, d))
+        # attention sinks: the memory keys / values [Hkv][M][dh] (plain fp32; read by the attention kernels)
+        M = int(getattr(c, 'num_mem_kv', 0))
+        if M:
+            for wl in self.wl:
+                wl.update(mem_k=z(self.Hkv, M, c.dim_head), mem_v=z(self.Hkv, M, c.dim_head))
         self._alloc_ff_images(z)
         self._pk_src += [(wl, k) for wl in self.wl for k in ('w_qkv', 'w_out', 'w_ff1', 'w_ff2')]
 
@@ -158,7 +163,8 @@ class RolloutEngine:
             layers[i] = L.DecodeLayer(*(self._wv(w, k) for k in ('ln_attn', 'w_qkv', 'b_qkv', 'w_out', 'ln_ff', 'w_ff1',
                                                                  'b_ff1', 'w_ff2', 'b_ff2')), rows(kc), rows(vc),
                                       self._wv(w, 'w_out_t'), self._wv(w, 'w_ff1x'), self._wv(w, 'w_ff2x'),
-                                      *(self._wv(w, k) for k in ('w_qkv_t', 'w_ff1_t', 'w_ff2_t', 'w_ff1f', 'w_ff2f')))
+                                      *(self._wv(w, k) for k in ('w_qkv_t', 'w_ff1_t', 'w_ff2_t', 'w_ff1f', 'w_ff2f',
+                                                                 'mem_k', 'mem_v')))
         D = L.DecodeDesc()
         D.E, D.S, D.A, D.B, D.d, D.L, D.H, D.dh, D.Tmax = (Eg, c.state_dim, c.num_actions, c.num_bins, c.dim,
                                                            c.depth, c.heads, c.dim_head, self.T)
@@ -172,6 +178,8 @@ class RolloutEngine:
         D.rms_norm = int(getattr(c, 'rms_norm', False))
         D.attn_window = int(getattr(c, 'attn_window', 0))   # sliding window (0: none)
         D.Hkv = self.Hkv                                     # kv heads (grouped-query attention; = H without)
+        # attention sinks: memory rows per kv head (XtrlDecodeLayer.mem_k / mem_v) and the zero key
+        D.num_mem_kv, D.add_zero_kv = int(getattr(c, 'num_mem_kv', 0)), int(bool(getattr(c, 'add_zero_kv', False)))
         D.sim_mode, D.hazard_log2, D.rs_eps = self.sim_mode, hazard_log2, 1e-5
         if clamp is not None:
             D.clamp_lo, D.clamp_hi, D.has_clamp = float(clamp[0]), float(clamp[1]), 1
@@ -232,6 +240,9 @@ class RolloutEngine:
                     bias.append(torch.zeros(self.Hkv, device=self.dev))
             torch.cat(rows, out=wl['w_qkv'])
             torch.cat(bias, out=wl['b_qkv'][:self.n_qkv])
+            if 'mem_k' in wl:   # attention sinks
+                wl['mem_k'].copy_(blk.mem_k)
+                wl['mem_v'].copy_(blk.mem_v)
             wl['w_out'].copy_(blk.to_out.weight)
             wl['w_out_t'].copy_(blk.to_out.weight.t())
             wl['ln_ff'].copy_(norm_gain(ln_f))
@@ -682,6 +693,7 @@ class FractalRolloutEngine(RolloutEngine):
         self.desc.state_only = 1
         self.desc.attn_window = 0   # (the fractal body has no sliding window)
         self.desc.Hkv = 0           # (nor grouped-query attention)
+        self.desc.num_mem_kv = self.desc.add_zero_kv = 0   # (nor attention sinks)
         Lv = self.levels
         levels = (L.FractalLevel * Lv)()
         names = [n for n, _ in L.FractalLevel._fields_]

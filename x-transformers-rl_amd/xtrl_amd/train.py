@@ -153,6 +153,7 @@ class FusedTrainStep:
             Ly.w_ff1, Ly.b_ff1 = off(f1 + 'weight'), off(f1 + 'bias')
             Ly.w_ff2, Ly.b_ff2 = off(pf + '1.ff.2.weight'), off(pf + '1.ff.2.bias')
             Ly.n_qkv, Ly.mix = n_qkv, int(mix)
+            Ly.mem_k, Ly.mem_v = off(pa + '1.mem_k'), off(pa + '1.mem_v')   # attention sinks (-1: none)
             for k, t in bufs.items():
                 setattr(Ly, k, t.data_ptr())
         self.layers = layers
@@ -190,6 +191,11 @@ class FusedTrainStep:
         D.rms_norm = int(c.rms_norm)
         D.attn_window = int(c.attn_window)   # sliding window (0: none)
         D.Hkv = int(c.n_kv_heads)            # kv heads (grouped-query attention; = H without)
+        # attention sinks: memory rows per kv head (their per-(episode, head) gradient partials), the zero key
+        D.num_mem_kv, D.add_zero_kv = int(getattr(c, 'num_mem_kv', 0)), int(bool(getattr(c, 'add_zero_kv', False)))
+        if D.num_mem_kv:
+            self.sink_ws = E(int(L.lib().xtrl_attn_sink_ws_floats(b_max, H, D.num_mem_kv, dh)))
+            D.sink_ws, D.sink_ws_floats = self.sink_ws.data_ptr(), self.sink_ws.numel()
         D.inv_freq = self.inv_freq.data_ptr()
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
@@ -401,6 +407,7 @@ class FractalTrainStep(FusedTrainStep):
         D.ln_final = -1
         D.attn_window = 0   # (the fractal body has no sliding window)
         D.Hkv = 0           # (nor grouped-query attention)
+        D.num_mem_kv = D.add_zero_kv = 0   # (nor attention sinks)
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
         D.part_floats = self.buf['part'].numel()
