@@ -492,8 +492,9 @@ def test_ff_dropout_mask_is_host_philox_stream(p, layer):
 
 def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, episodes=8, batch=4, seed=3,
                  hazard=3, mode='lander', dim=48, reward_dropout=0.5, gene_dim=8, agent_extra=None, fractal_levels=None,
-                 ff_mult=4, genes=3, shard_by_gene=False, ff_no_bias=False, ff_glu=False, wm_extra=None):
+                 ff_mult=4, genes=3, shard_by_gene=False, ff_no_bias=False, ff_glu=False, wm_extra=None, squash=True):
     """``fractal_levels``: the causal fractal policy body (policy_body='fractal') on both sides.
+    ``squash``: squash_continuous of the Learner / squash of the oracle (tanh-squashed continuous actions).
     ``ff_mult``: the feed-forward width through world_model['ff_mult'] (x-transformers' FeedForward mult).
     ``wm_extra``: further world_model options (attn_qk_norm, attn_qk_norm_scale, rotary_xpos,
     rotary_xpos_scale_base), given to the oracle's Decoder as well."""
@@ -520,7 +521,7 @@ def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, epi
     gp = dict(dim=gene_dim, num_genes_per_island=genes, num_selected=2, tournament_size=2)
     learner = Learner(state_dim=S, num_actions=A, reward_range=(-2., 2.), world_model=wm, max_timesteps=T,
                       batch_size=batch, num_episodes_per_update=episodes, evolutionary=evo, evolve_every=1,
-                      evolve_after_step=0, latent_gene_pool=gp, continuous_actions=cont,
+                      evolve_after_step=0, latent_gene_pool=gp, continuous_actions=cont, squash_continuous=squash,
                       continuous_actions_clamp=(-1., 1.) if cont else None,
                       agent_kwargs=dict(dropout=0., seed=seed, hidden_dim=dim, reward_dropout=reward_dropout,
                                         **(agent_extra or {})),
@@ -533,7 +534,8 @@ def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, epi
         learner.agent.ema_flat.copy_(learner.agent.flat.flat)
     env = SynthVecSim(S, A, mode, hazard_log2=hazard)
     c = R.LearnerConfig(S, A, (-2., 2.), dim=dim, depth=depth, gate_values=gates, value_residual=gates,
-                        learned_mix=gates, continuous=cont, clamp=(-1., 1.) if cont else None, evolutionary=evo,
+                        learned_mix=gates, continuous=cont, squash=squash, clamp=(-1., 1.) if cont else None,
+                        evolutionary=evo,
                         evolve_every=1, evolve_after_step=0, gene_pool=gp, max_timesteps=T, batch_size=batch,
                         num_episodes_per_update=episodes, sim_mode=mode, hazard_log2=hazard, seed=seed,
                         reward_dropout=reward_dropout, ff_mult=ff_mult, ff_no_bias=ff_no_bias, ff_glu=ff_glu,
@@ -1390,12 +1392,13 @@ def _config_parity(depth, dim, T, hazard, evo, episodes, batch, gene_dim=8, max_
     return seen, lens
 
 
-def _learn_parity(learner, oracle, traj, lens, genes, fit, max_minibatches, dropout=0., packed=False):
+def _learn_parity(learner, oracle, traj, lens, genes, fit, max_minibatches, dropout=0., packed=False, cont=False):
     """The first ``max_minibatches`` minibatches of Agent.learn against the oracle on the GPU's
     current weights, RSNorm, genes and minibatch (rebuilt from the device trajectory as
     xtrl.py:822-852 does): loss within 1e-4 relative, every gradient within 1e-4 of the gradient
     scale.  ``dropout`` > 0: the learn step runs with attention / FF dropout and the oracle applies
-    the same keep masks (oracle.philox.attn_dropout_keep / ff_dropout_keep) in its training forward."""
+    the same keep masks (oracle.philox.attn_dropout_keep / ff_dropout_keep) in its training forward.
+    ``cont``: continuous actions (the episodes are rebuilt from the trajectory's float actions)."""
     agent = learner.agent
     c = oracle.c
     evo = agent.evolutionary
@@ -1403,7 +1406,7 @@ def _learn_parity(learner, oracle, traj, lens, genes, fit, max_minibatches, drop
     agent.model.cfg.dropout = dropout
     gene_list = genes.cpu().tolist()
     states, actions, old_lp, rewards, bounds, values, elens, egenes = oracle_minibatch_tensors(
-        gpu_episodes(traj, lens, gene_list))
+        gpu_episodes(traj, lens, gene_list, cont))
     returns = R.calc_gae(rewards, oracle.model.hl(values), (~bounds).float(), c.gamma, c.lam)
     rs = R.RSNormState(c.state_dim + 1)
     rs.mean, rs.var = agent.rs_mean.cpu().clone(), agent.rs_var.cpu().clone()
