@@ -229,12 +229,22 @@ def test_sink_real_key_keep_bits_equal_a_run_without_sinks(p):
 # ----------------------------------------------------------------------------------------------
 
 CONFIGS = {'mem2+zero': (2, True), 'zero': (0, True)}   # (M, Z); both with W = 5 and kv_heads = 2
+# the same three tests (rollout + learn, packed learn, fused vs autograd) at dh != 16: (M, Z, make_sink_learner
+# keywords) — k_attn_decode<32|64, 0, true>, k_decode_row<32|64, ., true> and the learn step's sink kernels
+GEOM_CONFIGS = {'h4x32_gqa2_mem3+zero': (3, True, dict(heads=4, dim_head=32, Hkv=2, dim=64)),
+                'h2x64_kv1_zero': (0, True, dict(heads=2, dim_head=64, Hkv=1, dim=48))}
+ALL_CONFIGS = list(CONFIGS) + list(GEOM_CONFIGS)
+
+
+def config(cfg):
+    """(M, Z, make_sink_learner keywords) of a CONFIGS or GEOM_CONFIGS entry."""
+    return (*CONFIGS[cfg], {}) if cfg in CONFIGS else GEOM_CONFIGS[cfg]
 
 
 def make_sink_learner(M, Z, W=5, Hkv=2, depth=2, gates=True, T=24, episodes=6, batch=3, seed=3, hazard=4, mode='lander',
-                      dim=48, agent_extra=None, with_oracle=True):
+                      dim=48, agent_extra=None, with_oracle=True, heads=4, dim_head=16):
     """Learner with world_model attn_num_mem_kv = M, attn_add_zero_kv = Z, attn_max_attend_past = W and
-    agent_kwargs kv_heads = Hkv (H = 4, dh = 16), the device Sim and the oracle on the same weights
+    agent_kwargs kv_heads = Hkv (``heads`` x ``dim_head``, 4 x 16 by default), the device Sim and the oracle on the same weights
     (test_attn_gqa_gpu.make_gqa_learner's construction; the oracle takes the sinks, GQA and the window from
     the patched Attention, which the caller installs first).  The Sim's terminations depend on the seed
     alone: seed 3 at hazard 2^-4 gives the lengths 22, 24, 4, 12, 24, 21 in the minibatches (24, 21, 4) and
@@ -242,7 +252,7 @@ def make_sink_learner(M, Z, W=5, Hkv=2, depth=2, gates=True, T=24, episodes=6, b
     from xtrl_amd import Learner, SynthVecSim
     S, A = 8, 4
     torch.manual_seed(seed)
-    wm = dict(attn_dim_head=16, heads=4, depth=depth, attn_num_mem_kv=M, attn_add_zero_kv=Z)
+    wm = dict(attn_dim_head=dim_head, heads=heads, depth=depth, attn_num_mem_kv=M, attn_add_zero_kv=Z)
     if gates:
         wm.update(attn_gate_values=True, add_value_residual=True, learned_value_residual_mix=True)
     if W is not None:
@@ -261,8 +271,8 @@ def make_sink_learner(M, Z, W=5, Hkv=2, depth=2, gates=True, T=24, episodes=6, b
     env = SynthVecSim(S, A, mode, hazard_log2=hazard)
     if not with_oracle:
         return learner, env, None
-    c = R.LearnerConfig(S, A, (-2., 2.), dim=dim, depth=depth, gate_values=gates, value_residual=gates,
-                        learned_mix=gates, max_timesteps=T, batch_size=batch, num_episodes_per_update=episodes,
+    c = R.LearnerConfig(S, A, (-2., 2.), dim=dim, depth=depth, heads=heads, dim_head=dim_head, gate_values=gates,
+                        value_residual=gates, learned_mix=gates, max_timesteps=T, batch_size=batch, num_episodes_per_update=episodes,
                         sim_mode=mode, hazard_log2=hazard, seed=seed, reward_dropout=0.5, gene_pool=gp)
     sd = {k: v.detach().cpu() for k, v in learner.agent.model.state_dict().items()}
     oracle = R.OracleLearner(c, init_state_dict=sd)
@@ -279,16 +289,17 @@ def sink_rollout_and_learn(monkeypatch, M, Z, T, minibatches, packed=False, **kw
     ``minibatches`` learn minibatches (G._learn_parity: loss within 1e-4 relative, every gradient — mem_k /
     mem_v among them — within 1e-4 of the gradient scale) against the sink oracle.  ``packed``: the packed
     learn step (per-token critic reduction on both sides)."""
-    install_sink_oracle(monkeypatch, M, Z)
+    Hkv, dh = kw.get('Hkv', 2), kw.get('dim_head', 16)
+    install_sink_oracle(monkeypatch, M, Z, Hkv=Hkv)
     extra = dict(hl_reduction_mean=False, packed_learn=True) if packed else None
     learner, env, oracle = make_sink_learner(M, Z, T=T, agent_extra=extra, **kw)
     cfg = learner.agent.cfg
-    assert (cfg.num_mem_kv, cfg.add_zero_kv, cfg.attn_window, cfg.kv_heads) == (M, Z, 5, 2)
+    assert (cfg.num_mem_kv, cfg.add_zero_kv, cfg.attn_window, cfg.kv_heads, cfg.dim_head) == (M, Z, 5, Hkv, dh)
     traj, lens, genes, cum = learner.rollout_device(env, 0, T)
     torch.cuda.synchronize()
     eng = learner._engine_for(env, T)
     for kc, vc in eng.kv:   # the sinks are not cached
-        assert kc.shape == vc.shape == (eng.E, 2, T, 16)
+        assert kc.shape == vc.shape == (eng.E, Hkv, T, dh)
     episodes, _ = oracle.rollout(0)
     G.compare_rollout(traj, lens, episodes)
     seen = []
@@ -306,24 +317,26 @@ def sink_rollout_and_learn(monkeypatch, M, Z, T, minibatches, packed=False, **kw
 
 
 @pytest.mark.parametrize('rows', ['1', '0'])
-@pytest.mark.parametrize('cfg', list(CONFIGS))
+@pytest.mark.parametrize('cfg', ALL_CONFIGS)
 def test_sink_rollout_and_learn_match_oracle(cfg, rows, monkeypatch):
     """H = 4, kv_heads 2, W = 5, d = 48, depth 2 with gates and the learned mix, T = 24: both decode paths (the
     row-resident step and the multi-kernel step), then two padded learn minibatches, whose padded rows past
-    the band attend the sinks alone."""
+    the band attend the sinks alone.  GEOM_CONFIGS: the same at 4 x 32 heads (kv_heads 2, M = 3, d = 64) and at
+    2 x 64 heads (one kv head, the zero key alone, d = 48)."""
     monkeypatch.setenv('XTRL_DECODE_ROWS', rows)
-    M, Z = CONFIGS[cfg]
-    _, lens, seen = sink_rollout_and_learn(monkeypatch, M, Z, 24, 2)
+    M, Z, kw = config(cfg)
+    learner, lens, seen = sink_rollout_and_learn(monkeypatch, M, Z, 24, 2, **kw)
+    assert (learner._engine[1].rows_max > 0) == (rows == '1')
     assert int(lens.max()) > 10 and len(seen) == 2
     assert int(lens.min()) + 5 < max(s[0] for s in seen)   # an episode with rows past its band
 
 
-@pytest.mark.parametrize('cfg', list(CONFIGS))
+@pytest.mark.parametrize('cfg', ALL_CONFIGS)
 def test_sink_packed_learn_matches_oracle(cfg, monkeypatch):
     """The packed learn step (hl_reduction_mean=False, packed_learn=True) against the sink oracle: the row
     sums of dmem_k / dmem_v run over the valid rows."""
-    M, Z = CONFIGS[cfg]
-    learner, _, seen = sink_rollout_and_learn(monkeypatch, M, Z, 24, 2, packed=True)
+    M, Z, kw = config(cfg)
+    learner, _, seen = sink_rollout_and_learn(monkeypatch, M, Z, 24, 2, packed=True, **kw)
     assert learner.agent.packed_learn and len(seen) == 2
 
 
@@ -363,13 +376,13 @@ def test_sink_deploy_forward_matches_oracle_cached_decode(cfg, monkeypatch):
 
 
 @pytest.mark.parametrize('p', [0., 0.25])
-@pytest.mark.parametrize('cfg', list(CONFIGS))
+@pytest.mark.parametrize('cfg', ALL_CONFIGS)
 def test_sink_fused_step_matches_reference_mode_autograd(cfg, p):
     """The hand-scheduled learn step against the reference-mode autograd step (model.forward_train with
     ops.attention taking the sinks) with gates, W = 5, kv_heads 2, T = 24: the bounds of
     test_fused_train_step_matches_autograd, mem_k / mem_v among the gradients."""
-    M, Z = CONFIGS[cfg]
-    learner, env, _ = make_sink_learner(M, Z, T=24, episodes=8, batch=4, seed=9, dim=64, with_oracle=False)
+    M, Z, kw = config(cfg)
+    learner, env, _ = make_sink_learner(M, Z, T=24, episodes=8, batch=4, seed=9, with_oracle=False, **{'dim': 64, **kw})
     agent = learner.agent
     agent.cfg.dropout = p
     agent.model.cfg.dropout = p

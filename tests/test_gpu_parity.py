@@ -286,8 +286,12 @@ def attn_ref(q, k, v, lens, scale):
     return torch.einsum('bhij,bhjd->bhid', s.softmax(-1), v)
 
 
-@pytest.mark.parametrize('b,H,n,dh', [(3, 4, 37, 16), (2, 2, 130, 16), (2, 3, 64, 32), (1, 2, 70, 64), (4, 4, 128, 16)])
+@pytest.mark.parametrize('b,H,n,dh', [(3, 4, 37, 16), (2, 2, 130, 16), (2, 3, 64, 32), (1, 2, 70, 64), (4, 4, 128, 16),
+                                      # more than two key tiles at dh = 32 / 64 (n > 128: the long-episode backward dispatch)
+                                      (2, 2, 130, 32), (1, 2, 257, 32), (2, 2, 130, 64), (1, 2, 200, 64)])
 def test_attention_fwd_bwd(b, H, n, dh):
+    """dh != 16 at n > 128: also through the C ABI with every output filled with NaN before the call — all
+    finite afterwards, and within the same bounds."""
     from xtrl_amd import ops
     g = torch.Generator().manual_seed(n + dh)
     q, k, v, do = (torch.randn(b, H, n, dh, generator=g).to(DEV) for _ in range(4))
@@ -306,17 +310,28 @@ def test_attention_fwd_bwd(b, H, n, dh):
     tol(qf.grad, qd.grad, 1e-4, 1e-5)
     tol(kf.grad, kd.grad, 1e-4, 1e-5)
     tol(vf.grad, vd.grad, 1e-4, 1e-5)
+    if dh != 16 and n > 128:
+        res = _attn_bwd_lib(q, k, v, lens, do, scale, 0., False, nan_fill=True)
+        for name, t in res.items():
+            assert torch.isfinite(t).all(), name
+        tol(res['o'], ref, 1e-5, 1e-5)
+        for name, r in (('dq', qd.grad), ('dk', kd.grad), ('dv', vd.grad)):
+            tol(res[name], r, 1e-4, 1e-5)
 
 
-def _attn_bwd_lib(q, k, v, lens, do, scale, p, fused, seed=3, offset=1, sub=0):
+def _attn_bwd_lib(q, k, v, lens, do, scale, p, fused, seed=3, offset=1, sub=0, nan_fill=False):
     """xtrl_attn_fwd + xtrl_attn_bwd through the C ABI, the backward as the fused one-launch kernel
-    (XTRL_ATTN_FUSED_BWD=1, read per launch) or the dK/dV + dQ kernel pair."""
+    (XTRL_ATTN_FUSED_BWD=1, read per launch) or the dK/dV + dQ kernel pair.  ``nan_fill``: every output
+    holds NaN before the calls."""
     import os
     from xtrl_amd import _lib as L
     lib = L.lib()
     b, H, n, dh = q.shape
     o, dq, dk, dv = (torch.empty_like(q) for _ in range(4))
     lse, delta = (torch.empty(b, H, n, device=DEV) for _ in range(2))
+    if nan_fill:
+        for t in (o, dq, dk, dv, lse, delta):
+            t.fill_(float('nan'))
     L.check(lib.xtrl_attn_fwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), b, H, n, dh, scale, p,
                               seed, offset, sub, L.stream()), 'attn_fwd')
     old = os.environ.get('XTRL_ATTN_FUSED_BWD')
@@ -461,6 +476,45 @@ def test_attention_dropout_mask_is_host_philox_stream(p):
     tol(vf.grad, vd.grad, 1e-4, 1e-5)
 
 
+@pytest.mark.parametrize('p', [0.25, 0.1])
+@pytest.mark.parametrize('dh', [32, 64])
+def test_attention_dropout_dh32_64_against_host_keep_bits(dh, p):
+    """Dropout at dh = 32 / 64 over three key tiles (n = 130; p = 0.25: byte mode, 0.1: word mode): the forward
+    and the q / k / v gradients of ops.attention against the fp64 softmax times the host keep bits
+    (oracle.philox.attn_dropout_keep), at the bounds of test_attn_sink_gpu.test_sink_dropout_against_host_keep_bits
+    (o 1e-5 + 1e-5, gradients 1e-4 + 1e-5); and through the C ABI with every output NaN-filled before the
+    calls: all finite afterwards, within the same bounds."""
+    from xtrl_amd import ops
+    from oracle import philox as P
+    g = torch.Generator().manual_seed(13 + dh)
+    b, H, n = 2, 2, 130
+    q, k, v, do = (torch.randn(b, H, n, dh, generator=g) for _ in range(4))
+    lens = torch.tensor([n, 77], dtype=torch.int32)
+    seed, offset, scale, layer = 1234567, 5, dh ** -0.5, 3
+    keep = P.attn_dropout_keep(b, H, n, p, seed, offset, layer)
+    assert abs(keep.mean() - (1 - p)) < 0.02
+    keep_t = torch.from_numpy(keep).double() / (1 - p)
+    qd, kd, vd = (t.double().requires_grad_() for t in (q, k, v))
+    s = torch.einsum('bhid,bhjd->bhij', qd, kd) * scale
+    ii = torch.arange(n)
+    valid = (ii[None, :] <= ii[:, None])[None, None] & (ii[None, None, None, :] < lens.long()[:, None, None, None])
+    ref = torch.einsum('bhij,bhjd->bhid', s.masked_fill(~valid, float('-inf')).softmax(-1) * keep_t, vd)
+    (ref * do.double()).sum().backward()
+    qf, kf, vf = (t.to(DEV).requires_grad_() for t in (q, k, v))
+    out = ops.attention(qf, kf, vf, lens.to(DEV), scale, p, seed=seed, offset=offset, sub=layer)
+    (out * do.to(DEV)).sum().backward()
+    res = _attn_bwd_lib(q.to(DEV), k.to(DEV), v.to(DEV), lens.to(DEV), do.to(DEV), scale, p, False, seed=seed,
+                        offset=offset, sub=layer, nan_fill=True)
+    torch.cuda.synchronize()
+    for name, t in list(res.items()) + [('out', out), ('qg', qf.grad), ('kg', kf.grad), ('vg', vf.grad)]:
+        assert torch.isfinite(t).all(), name
+    for o_, gq, gk, gv in ((out, qf.grad, kf.grad, vf.grad), (res['o'], res['dq'], res['dk'], res['dv'])):
+        tol(o_, ref, 1e-5, 1e-5)
+        tol(gq, qd.grad, 1e-4, 1e-5)
+        tol(gk, kd.grad, 1e-4, 1e-5)
+        tol(gv, vd.grad, 1e-4, 1e-5)
+
+
 @pytest.mark.parametrize('p,layer', [(0.25, 0), (0.1, 0), (0.25, 5), (0.1, 2)])
 def test_ff_dropout_mask_is_host_philox_stream(p, layer):
     """FF dropout keep mask (xtrl_ff_dropout_mask, the bits the GELU_DROP GEMM epilogue draws) equals
@@ -492,8 +546,12 @@ def test_ff_dropout_mask_is_host_philox_stream(p, layer):
 
 def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, episodes=8, batch=4, seed=3,
                  hazard=3, mode='lander', dim=48, reward_dropout=0.5, gene_dim=8, agent_extra=None, fractal_levels=None,
-                 ff_mult=4, genes=3, shard_by_gene=False, ff_no_bias=False, ff_glu=False, wm_extra=None, squash=True):
-    """``fractal_levels``: the causal fractal policy body (policy_body='fractal') on both sides.
+                 ff_mult=4, genes=3, shard_by_gene=False, ff_no_bias=False, ff_glu=False, wm_extra=None, squash=True,
+                 heads=4, dim_head=16, device=None):
+    """``heads``, ``dim_head``: the attention geometry (world_model heads / attn_dim_head and the oracle's
+    LearnerConfig fields).  ``device``: 'cpu' builds the Learner without a GPU (the same initial weights:
+    test_geometry_cpu settles the cases' inputs from the oracle alone).
+    ``fractal_levels``: the causal fractal policy body (policy_body='fractal') on both sides.
     ``squash``: squash_continuous of the Learner / squash of the oracle (tanh-squashed continuous actions).
     ``ff_mult``: the feed-forward width through world_model['ff_mult'] (x-transformers' FeedForward mult).
     ``wm_extra``: further world_model options (attn_qk_norm, attn_qk_norm_scale, rotary_xpos,
@@ -505,7 +563,7 @@ def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, epi
         assert not gates
         agent_extra = dict(agent_extra or {}, policy_body='fractal', fractal_levels=fractal_levels)
         factory = lambda mc: FR.OracleFractalPolicy(mc, fractal_levels)   # noqa: E731
-    wm = dict(attn_dim_head=16, heads=4, depth=depth)
+    wm = dict(attn_dim_head=dim_head, heads=heads, depth=depth)
     if ff_mult != 4:
         wm['ff_mult'] = ff_mult
     if ff_no_bias:
@@ -525,7 +583,8 @@ def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, epi
                       continuous_actions_clamp=(-1., 1.) if cont else None,
                       agent_kwargs=dict(dropout=0., seed=seed, hidden_dim=dim, reward_dropout=reward_dropout,
                                         **(agent_extra or {})),
-                      use_graph=False, shard_by_gene=shard_by_gene)
+                      use_graph=False, shard_by_gene=shard_by_gene,
+                      **(dict(accelerate_kwargs=dict(device=device)) if device is not None else {}))
     with torch.no_grad():   # non-trivial gate / mix weights (their init is constant)
         g = torch.Generator().manual_seed(seed + 1)
         for name, p in learner.agent.model.named_parameters():
@@ -533,10 +592,9 @@ def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, epi
                 p.copy_((torch.randn(p.shape, generator=g) * 0.3).to(p.device))
         learner.agent.ema_flat.copy_(learner.agent.flat.flat)
     env = SynthVecSim(S, A, mode, hazard_log2=hazard)
-    c = R.LearnerConfig(S, A, (-2., 2.), dim=dim, depth=depth, gate_values=gates, value_residual=gates,
-                        learned_mix=gates, continuous=cont, squash=squash, clamp=(-1., 1.) if cont else None,
-                        evolutionary=evo,
-                        evolve_every=1, evolve_after_step=0, gene_pool=gp, max_timesteps=T, batch_size=batch,
+    c = R.LearnerConfig(S, A, (-2., 2.), dim=dim, depth=depth, heads=heads, dim_head=dim_head, gate_values=gates,
+                        value_residual=gates, learned_mix=gates, continuous=cont, squash=squash,
+                        clamp=(-1., 1.) if cont else None, evolutionary=evo, evolve_every=1, evolve_after_step=0, gene_pool=gp, max_timesteps=T, batch_size=batch,
                         num_episodes_per_update=episodes, sim_mode=mode, hazard_log2=hazard, seed=seed,
                         reward_dropout=reward_dropout, ff_mult=ff_mult, ff_no_bias=ff_no_bias, ff_glu=ff_glu,
                         **oracle_extra)
@@ -1336,9 +1394,11 @@ def test_ff_glu_fused_train_step_matches_autograd():
     _fused_vs_autograd(False, True, True, 0.25, 70, depth=2, episodes=16, batch=16, hazard=6, dim=128, ff_glu=True)
 
 
-def _fused_vs_autograd(cont, evo, gates, p, T, depth, episodes, batch, hazard, dim, fractal=None, ff_glu=False):
+def _fused_vs_autograd(cont, evo, gates, p, T, depth, episodes, batch, hazard, dim, fractal=None, ff_glu=False, **geom):
+    """``geom``: further make_learner keywords (S, A, heads, dim_head, ff_mult, squash: test_geometry_gpu)."""
     learner, env, _ = make_learner(depth=depth, gates=gates, evo=evo, cont=cont, T=T, episodes=episodes,
-                                   batch=batch, seed=9, hazard=hazard, dim=dim, fractal_levels=fractal, ff_glu=ff_glu)
+                                   batch=batch, seed=9, hazard=hazard, dim=dim, fractal_levels=fractal, ff_glu=ff_glu,
+                                   **geom)
     agent = learner.agent
     agent.cfg.dropout = p
     agent.model.cfg.dropout = p
@@ -1353,6 +1413,7 @@ def _fused_vs_autograd(cont, evo, gates, p, T, depth, episodes, batch, hazard, d
     for name, (s, e) in agent.flat.index.items():
         err = float((a['grad'][s:e] - b['grad'][s:e]).abs().max())
         assert err <= 1e-4 * scale + 1e-7, (name, err, scale)
+    return lens.cpu()
 
 
 @pytest.mark.gpu
@@ -1600,13 +1661,19 @@ def test_packed_learn_matches_padded_step(evo, gates, T, dim, cont, wm):
     actor / critic outputs on the valid tokens (zeros on the padding for the packed step) and every
     gradient tensor within 1e-4 of its own scale.  T 150: key tiles past 128 (the long-episode
     attention backward with per-episode rows)."""
+    _packed_vs_padded(evo, gates, T, dim, cont, wm)
+
+
+def _packed_vs_padded(evo, gates, T, dim, cont, wm, depth=2, **geom):
+    """The body of test_packed_learn_matches_padded_step; ``depth`` and ``geom`` (S, A, heads, dim_head, ...):
+    further make_learner keywords (test_geometry_gpu)."""
     res = {}
     glu = bool((wm or {}).get('ff_glu', False))
     extra = {k: v for k, v in (wm or {}).items() if k != 'ff_glu'} or None
     for packed in (False, True):
-        learner, env, _ = make_learner(depth=2, gates=gates, evo=evo, T=T, episodes=8, batch=8, seed=5, hazard=5,
+        learner, env, _ = make_learner(depth=depth, gates=gates, evo=evo, T=T, episodes=8, batch=8, seed=5, hazard=5,
                                        dim=dim, cont=cont, ff_glu=glu, wm_extra=extra,
-                                       agent_extra=dict(hl_reduction_mean=False, packed_learn=packed))
+                                       agent_extra=dict(hl_reduction_mean=False, packed_learn=packed), **geom)
         agent = learner.agent
         traj, lens, genes, cum = learner.rollout_device(env, 0, T)
         res[packed] = _first_minibatch_state(agent, traj, lens, genes, learner.fitness(cum, genes))
