@@ -27,6 +27,27 @@ def test_library_exports_every_declared_symbol():
     assert lib.xtrl_abi_version() == _lib.ABI_VERSION
 
 
+def test_env_switches_are_documented():
+    """The XTRL_* variables the package reads (a getenv( / os.environ read under csrc/ and xtrl_amd/)
+    are exactly the first column of DESIGN.md's "Runtime switches" table."""
+    pkg = REPO / 'x-transformers-rl_amd'
+    read = set()
+    for sub, pats in (('csrc', ('*.hip', '*.h', '*.cpp')), ('xtrl_amd', ('*.py',))):
+        for pat in pats:
+            for f in sorted((pkg / sub).glob(pat)):
+                for line in f.read_text().splitlines():
+                    if 'getenv(' in line or 'os.environ' in line:
+                        read |= set(re.findall(r'XTRL_[A-Z0-9_]+', line))
+    design = (REPO / 'DESIGN.md').read_text()
+    section = design.split('### Runtime switches', 1)[1].split('\n#', 1)[0]
+    rows = [l for l in section.splitlines() if l.startswith('|')][2:]   # (past the header and its rule)
+    documented = {re.fullmatch(r'`(XTRL_[A-Z0-9_]+)`', l.split('|')[1].strip()).group(1) for l in rows}
+    assert len(documented) == len(rows)
+    assert read - documented == set(), 'read by the package, missing from the DESIGN.md table'
+    assert documented - read == set(), 'in the DESIGN.md table, no longer read by the package'
+    assert len(read) >= 10
+
+
 @pytest.mark.parametrize('T,b,d,A', [(64 * 500, 64, 128, 1), (16384, 128, 256, 4), (10, 2, 48, 2), (17, 1, 8, 16)])
 def test_train_partial_workspace_covers_every_reduction(T, b, d, A):
     """xtrl_train_part_floats (host-only) states the partial-sum floats a learn step needs: the

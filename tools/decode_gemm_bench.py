@@ -1,5 +1,4 @@
-"""Decode-step GEMM shapes (M = envs) through xtrl_gemm_f32 with the decode epilogues; geometry is
-forced with XTRL_GEMM_GEOM (tuning)."""
+"""Decode-step GEMM shapes (M = envs) through xtrl_gemm_f32 with the decode epilogues."""
 import os, sys
 sys.path[:0] = ['.', 'x-transformers-rl_amd']
 import torch
@@ -26,7 +25,6 @@ def launch(X, wk, bias, ln, Rr, act, N, K):
                               L.ptr(Rr), Rr.stride(0) if Rr is not None else 0, L.ptr(y), N, None, 0, E, N, K, act,
                               L.stream()))
 
-geom = os.environ.get('XTRL_GEMM_GEOM', 'auto')
 for tag, X, wk, bias, ln, Rr, act, N, K in cases:
     f = lambda: launch(X, wk, bias, ln, Rr, act, N, K)
     f(); torch.cuda.synchronize()
@@ -38,4 +36,4 @@ for tag, X, wk, bias, ln, Rr, act, N, K in cases:
     s.record()
     gr.replay()
     e.record(); torch.cuda.synchronize()
-    print(f'geom {geom:4s} {tag:12s} M={E} N={N} K={K}: {s.elapsed_time(e) / 50 * 1e3:7.1f} us')
+    print(f'{tag:12s} M={E} N={N} K={K}: {s.elapsed_time(e) / 50 * 1e3:7.1f} us')

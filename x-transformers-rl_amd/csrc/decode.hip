@@ -1138,13 +1138,18 @@ __device__ __forceinline__ void frag_pieces(const uint4 (&w)[WR], uint4 (&b)[3])
 }
 
 // FI: the weights come from the fp32 fragment images (Ly.w_ff1f / w_ff2f: 2/3 of the split images'
-// bytes, the split done per fragment before its MFMAs) instead of the split images.  EW (FI only):
-// the W2 fragments are loaded in the same batch as W1 (one weight round trip instead of two; 256
-// registers of weights: one workgroup per SIMD set)
-template <int NT2, int MT, bool FI, bool EW = false>   // d = 64 NT2 (d <= 256): output columns per wave 16 NT2; panel rows 16 MT
-__global__ __launch_bounds__(256, EW ? 1 : 2) void k_mlp(const XtrlDecodeDesc D, const XtrlDecodeLayer Ly, int t, const float* xin,
-                                             const float* res, float* C, int ldc, const float* g_next, float* Y,
-                                             int ldy, const FrMlp fm) {
+// bytes, the split done per fragment before its MFMAs) instead of the split images.  Panels of 16
+// rows: 32-row panels (every weight fragment fed to twice the rows on half the workgroups) measured
+// slower at C3 (26.2 vs 19.7 us a launch, rollout 26.5 vs 23.2 ms: the per-wave MFMA chain doubles
+// and one workgroup per CU is left)
+template <int NT2, bool FI>   // d = 64 NT2 (d <= 256): output columns per wave 16 NT2
+__global__ __launch_bounds__(256, 2) void k_mlp(const XtrlDecodeDesc D, const XtrlDecodeLayer Ly, int t, const float* xin,
+                                                const float* res, float* C, int ldc, const float* g_next, float* Y,
+                                                int ldy, const FrMlp fm) {
+  // (MT = 1: the loops over the panel's 16-row tiles run once.  They stay because the compiler's
+  // register allocation follows the loop nest: without them the same instructions come out in other
+  // registers, and this kernel's code is kept as measured)
+  constexpr int MT = 1;
   constexpr int d = 64 * NT2, NT1 = MLP_HW / 64, BM = 16 * MT;
   constexpr int LDA = d + 4, JS1 = d / 32;              // FF1: K = d, 32-deep k steps
   constexpr int LDH = MLP_HW + 4, JSC = MLP_HW / 32;    // FF2: the chunk's 128 k
@@ -1178,8 +1183,8 @@ __global__ __launch_bounds__(256, EW ? 1 : 2) void k_mlp(const XtrlDecodeDesc D,
       for (int pc = 0; pc < WR; ++pc) bw[nt][s][pc] = wp[pc * P1 + 64 * s];
     b1v[nt] = Ly.b_ff1[t16 * 16 + lr];
   }
-  // this wave's W2 fragments: tiles w NT2 + nt, k steps of chunk c (EW: in this batch; else issued
-  // after FF1: with the first batch they would double the registers)
+  // this wave's W2 fragments: tiles w NT2 + nt, k steps of chunk c (issued after FF1: with the
+  // first batch they would double the registers)
   const uint4* w2 = reinterpret_cast<const uint4*>(FI ? (const void*)Ly.w_ff2f : (const void*)Ly.w_ff2x);
   const int64_t P2 = (int64_t)(d / 16) * JS2 * 64;
   uint4 b2w[NT2][JSC][WR];
@@ -1193,7 +1198,6 @@ __global__ __launch_bounds__(256, EW ? 1 : 2) void k_mlp(const XtrlDecodeDesc D,
         for (int pc = 0; pc < WR; ++pc) b2w[nt][s][pc] = wp[pc * P2 + 64 * s];
     }
   };
-  if constexpr (EW) load_w2();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   // ---- FF1 chunk + GELU -> Hs
@@ -1226,7 +1230,7 @@ __global__ __launch_bounds__(256, EW ? 1 : 2) void k_mlp(const XtrlDecodeDesc D,
           Hs[(16 * mt + 4 * q + i) * LDH + w * 16 * NT1 + 16 * nt + lr] =
               geluf_((acc[mt][nt][0][i] + acc[mt][nt][1][i]) + b1v[nt]);
   }
-  if constexpr (!EW) load_w2();
+  load_w2();
   __syncthreads();   // (Hs complete)
   // ---- FF2 partial of the chunk -> sc1 stores
   {
@@ -1388,26 +1392,6 @@ __global__ __launch_bounds__(256, EW ? 1 : 2) void k_mlp(const XtrlDecodeDesc D,
   }
 }
 
-// panel rows of the fused feed-forward: 16; XTRL_MLP_ROWS=32 (experiments) feeds every weight
-// fragment to twice the rows on half the workgroups — measured slower at C3 (26.2 vs 19.7 us a
-// launch, rollout 26.5 vs 23.2 ms: the per-wave MFMA chain doubles and one workgroup per CU is left)
-int mlp_rows() {
-  static const int r = [] {
-    const char* e = getenv("XTRL_MLP_ROWS");
-    return (e && atoi(e) == 32) ? 32 : 16;
-  }();
-  return r;
-}
-
-// XTRL_MLP_EW=1: the fp32-image feed-forward loads W1 and W2 in one batch (one workgroup per SIMD set)
-bool mlp_ew() {
-  static const bool on = [] {
-    const char* e = getenv("XTRL_MLP_EW");
-    return e && atoi(e) == 1;
-  }();
-  return on;
-}
-
 // the one-launch feed-forward's weights: the fp32 fragment images (preferred) or the split images
 bool mlp_weights(const XtrlDecodeLayer& Ly) { return (Ly.w_ff1f && Ly.w_ff2f) || (Ly.w_ff1x && Ly.w_ff2x); }
 
@@ -1423,19 +1407,13 @@ bool mlp_fused(const XtrlDecodeDesc* D, int l) {
 // (Y non-NULL) the pre-norm LN(C) g into Y
 int launch_mlp_rows(const XtrlDecodeDesc* D, int l, int t, const float* xin, const float* res, float* C, int ldc,
                     const float* g, float* Y, int ldy, hipStream_t s, const FrMlp& fm = FrMlp{}) {
-  const int bm = mlp_rows();
-  const dim3 grid(D->ff / MLP_HW, (D->E + bm - 1) / bm);
+  const dim3 grid(D->ff / MLP_HW, (D->E + 15) / 16);
   const XtrlDecodeLayer& Ly = D->layers[l];
   const bool fi = Ly.w_ff1f && Ly.w_ff2f;
 #define XTRL_MLP(NT2)                                                                              \
   do {                                                                                             \
-    if (bm == 32 && fi)                                                                            \
-      hipLaunchKernelGGL((k_mlp<NT2, 2, true>), grid, dim3(256), 0, s, *D, Ly, t, xin, res, C, ldc, g, Y, ldy, fm); \
-    else if (bm == 32)                                                                             \
-      hipLaunchKernelGGL((k_mlp<NT2, 2, false>), grid, dim3(256), 0, s, *D, Ly, t, xin, res, C, ldc, g, Y, ldy, fm); \
-    else if (fi && mlp_ew()) hipLaunchKernelGGL((k_mlp<NT2, 1, true, true>), grid, dim3(256), 0, s, *D, Ly, t, xin, res, C, ldc, g, Y, ldy, fm); \
-    else if (fi) hipLaunchKernelGGL((k_mlp<NT2, 1, true>), grid, dim3(256), 0, s, *D, Ly, t, xin, res, C, ldc, g, Y, ldy, fm); \
-    else hipLaunchKernelGGL((k_mlp<NT2, 1, false>), grid, dim3(256), 0, s, *D, Ly, t, xin, res, C, ldc, g, Y, ldy, fm); \
+    if (fi) hipLaunchKernelGGL((k_mlp<NT2, true>), grid, dim3(256), 0, s, *D, Ly, t, xin, res, C, ldc, g, Y, ldy, fm); \
+    else hipLaunchKernelGGL((k_mlp<NT2, false>), grid, dim3(256), 0, s, *D, Ly, t, xin, res, C, ldc, g, Y, ldy, fm); \
   } while (0)
   switch (D->d / 64) {
     case 1: XTRL_MLP(1); break;
@@ -1738,8 +1716,7 @@ int decode_heads(const XtrlDecodeDesc* D, int t, bool final_norm, hipStream_t s)
     const int bn = 64 / ks;
     const dim3 grid((g.N + bn - 1) / bn, (E + 15) / 16);
     const size_t lds = dg_lds_floats(1, 1, ks, false, g.K) * sizeof(float);
-    if (ks == 4) hipLaunchKernelGGL(k_heads_sample<4>, grid, dim3(256), lds, s, g, *D, t);
-    else if (ks == 2) hipLaunchKernelGGL(k_heads_sample<2>, grid, dim3(256), lds, s, g, *D, t);
+    if (ks == 2) hipLaunchKernelGGL(k_heads_sample<2>, grid, dim3(256), lds, s, g, *D, t);
     else hipLaunchKernelGGL(k_heads_sample<1>, grid, dim3(256), lds, s, g, *D, t);
     XTRL_LAUNCHED("heads_sample");
     return XTRL_OK;

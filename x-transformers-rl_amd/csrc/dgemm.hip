@@ -115,7 +115,6 @@ void dispatch_dg(const DGemmArgs& a, int rows, hipStream_t s) {
   const int ks = dg_ks(a.N, a.K);
   if (a.N >= 512 && lds32 <= 80 * 1024) launch_dg<2, 1, 1, EPI, LN, RES>(a, rows, s);
   else if (ks == 2) launch_dg<1, 1, 2, EPI, LN, RES>(a, rows, s);
-  else if (ks == 4) launch_dg<1, 1, 4, EPI, LN, RES>(a, rows, s);
   else launch_dg<1, 1, 1, EPI, LN, RES>(a, rows, s);
 }
 
@@ -123,16 +122,8 @@ void dispatch_dg(const DGemmArgs& a, int rows, hipStream_t s) {
 
 // the K split of a 16-row-panel projection: 2 for K >= 768 over N < 512 (FF2 at 440 live rows:
 // 9.7 -> 7.3 us; 4: 7.3 us at 440 rows but 14.0 vs 10.0 us at 1024, every column block re-reading
-// the A panel); XTRL_DG_KS overrides (1, 2, 4; experiments)
-int dg_ks(int N, int K) {
-  static const int ks_env = [] {
-    const char* e = getenv("XTRL_DG_KS");
-    const int v = e ? atoi(e) : 0;
-    return (v == 1 || v == 2 || v == 4) ? v : 0;
-  }();
-  if (!dg_split_k(N, K)) return 1;
-  return ks_env ? ks_env : 2;
-}
+// the A panel)
+int dg_ks(int N, int K) { return dg_split_k(N, K) ? 2 : 1; }
 
 int64_t dgemm_packed_floats(int N, int K) { return (int64_t)((N + 15) / 16) * 16 * dg_kp(K); }
 

@@ -1440,14 +1440,6 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_multi(const SplitKJobs J)
   }
 }
 
-bool xcd_env() {   // XTRL_GEMM_XCD=0: hardware workgroup order (A/B experiments)
-  static const bool on = [] {
-    const char* e = getenv("XTRL_GEMM_XCD");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
-}
-
 template <int WM, int WN, int WK, int TM, int TN, bool TA, bool TB, int EPI, bool LN, bool RES, bool VEC,
           bool X6 = false>
 void launch(const GemmArgs& a, hipStream_t s) {
@@ -1455,7 +1447,7 @@ void launch(const GemmArgs& a, hipStream_t s) {
   const int splits = a.kspan > 0 ? (a.K + a.kspan - 1) / a.kspan : 1;
   dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, splits);
   if constexpr (X6) {
-    if (xcd_env() && (int64_t)grid.x * grid.y * grid.z % 8 == 0) {
+    if ((int64_t)grid.x * grid.y * grid.z % 8 == 0) {
       GemmArgs r = a;
       r.xcd_remap = 1;
       hipLaunchKernelGGL((k_gemm<WM, WN, WK, TM, TN, TA, TB, EPI, LN, RES, VEC, X6>), grid, dim3(64 * WM * WN * WK), 0,
@@ -1467,37 +1459,17 @@ void launch(const GemmArgs& a, hipStream_t s) {
                      a);
 }
 
-// split-bf16 products on the 64 x 64 geometry too (XTRL_GEMM_X6_SMALL=0: f32 products there).  On
-// since the rollout's projections moved to the decode GEMM (dgemm.hip): the learn step's mid-sized
-// GEMMs gain (C3 learn -0.2 ... -0.5 ms in 5 of 5 A/B rounds); round 1 had it off for the decode
-// shapes (rollout 38.7 vs 38.1 ms)
-bool use_x6_small() {
-  static const bool on = [] {
-    const char* e = getenv("XTRL_GEMM_X6_SMALL");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
-}
-
-bool use_ws() {   // XTRL_GEMM_WS=0: the register-staged X6 kernel instead of the warp-specialised one
-  static const bool on = [] {
-    const char* e = getenv("XTRL_GEMM_WS");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
-}
-
 // the warp-specialised X6 kernel takes whole 32-deep slabs (K and the split span) and no LN prologue
 // (ta: the weight-gradient "T" x "T" layout, whose staging loads every k row on its own — a K that is not
 // a multiple of 32 (the packed learn step's token count) takes the KT variant, the last slab's rows past K
 // zeroed; spans stay multiples of 32)
 bool ws_ok(const GemmArgs& a, bool ta, bool ln) {
-  if (!(use_ws() && !ln && (a.K % 32 == 0 || ta) && (a.kspan == 0 || a.kspan % 32 == 0) && (!a.rowsum || ta)))
+  if (!(!ln && (a.K % 32 == 0 || ta) && (a.kspan == 0 || a.kspan % 32 == 0) && (!a.rowsum || ta)))
     return false;
   // one workgroup per CU: it wins only when the whole grid is one resident round and K is long
   // (16384 x 256 x 1024: 59 vs 72 us); with several rounds or K = 256 the register-staged kernel's
   // two workgroups per CU overlap one tile's prologue / epilogue with another's main loop
-  // (16384 x 1024 x 256: 94 vs 70 us; tools/gemm_bench.py, XTRL_GEMM_WS=0)
+  // (16384 x 1024 x 256: 94 vs 70 us; tools/gemm_bench.py)
   const int splits = a.kspan > 0 ? (a.K + a.kspan - 1) / a.kspan : 1;
   const int64_t wgs = (int64_t)((a.N + 127) / 128) * ((a.M + 127) / 128) * splits;
   // (weight gradients, "T" x "T": the warp-specialised kernel wins at every split span measured, down to
@@ -1522,7 +1494,7 @@ void launch_ws(const GemmArgs& a, hipStream_t s) {
   const int splits = a.kspan > 0 ? (a.K + a.kspan - 1) / a.kspan : 1;
   dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, splits);
   GemmArgs r = a;
-  r.xcd_remap = (xcd_env() && (int64_t)grid.x * grid.y * grid.z % 8 == 0) ? 1 : 0;
+  r.xcd_remap = (int64_t)grid.x * grid.y * grid.z % 8 == 0 ? 1 : 0;
   if constexpr (!TA && (EPI == EPI_NONE || EPI == EPI_RES_LN || EPI == EPI_LN_BWD || EPI == EPI_LN_BWD2)) {
     if (a.wimg && a.wimg_bn == BN && a.kspan == 0 && wimg_on()) {
       ++g_wimg_launches;
@@ -1583,32 +1555,10 @@ bool use_x6() {   // XTRL_GEMM_F32=1: native f32 MFMA products everywhere
 // the chip, else 64 x 64 tiles, else (decode-sized M) 64 x 32 tiles with a 2-way or 32 x 32 tiles
 // with a 4-way split of K inside the workgroup.  Operands whose contiguous extent is not a multiple of 4 (or unaligned) take
 // the scalar-load variant, instantiated for the 64 x 64 geometry only.
-int forced_geom() {   // XTRL_GEMM_GEOM=<n> (tuning experiments): force geometry n for VEC launches
-  static int g = [] {
-    const char* e = getenv("XTRL_GEMM_GEOM");
-    return e ? atoi(e) : -1;
-  }();
-  return g;
-}
-
 template <bool TA, bool TB, int EPI, bool LN, bool RES>
 void dispatch_geom(const GemmArgs& a, bool vec, hipStream_t s) {
   const int64_t tiles128 = (int64_t)((a.M + 127) / 128) * ((a.N + 127) / 128);
   const int64_t tiles64 = (int64_t)((a.M + 63) / 64) * ((a.N + 63) / 64);
-  const int fg = vec ? forced_geom() : -1;
-  if (fg >= 0 && !TA) {
-    switch (fg) {
-      case 0: launch<1, 1, 4, 1, 1, TA, TB, EPI, LN, RES, true>(a, s); return;
-      case 1: launch<2, 2, 1, 1, 1, TA, TB, EPI, LN, RES, true>(a, s); return;
-      case 2: launch<2, 2, 1, 2, 2, TA, TB, EPI, LN, RES, true>(a, s); return;
-      case 3: launch<1, 1, 2, 1, 1, TA, TB, EPI, LN, RES, true>(a, s); return;
-      case 4: launch<1, 2, 2, 1, 1, TA, TB, EPI, LN, RES, true>(a, s); return;
-      case 5: launch<2, 1, 2, 1, 1, TA, TB, EPI, LN, RES, true>(a, s); return;
-      case 6: launch<1, 1, 8, 1, 1, TA, TB, EPI, LN, RES, true>(a, s); return;
-      case 7: launch<1, 2, 4, 1, 1, TA, TB, EPI, LN, RES, true>(a, s); return;
-      default: break;
-    }
-  }
   // (decode-sized M measured on MI355X, graph-timed: M=1024 N=1024 K=256 64x64 11.6 us vs
   //  32x32/WK4 17.4; N=260 K=256 64x32/WK2 7.7 vs 8.2; N=256 K=1024 32x32/WK4 13.7 vs 64x64 24.7)
   // (learn shapes, tools/geom_probe.py learn: N <= 32 outputs over 16384 rows 64x32/WK2 9.8-10.8 us vs
@@ -1629,10 +1579,12 @@ void dispatch_geom(const GemmArgs& a, bool vec, hipStream_t s) {
   }
   else if (tiles64 >= 256 && a.K <= 512) {
     bool done = false;
-    // 64 x 64 tiles with split-bf16 products (XTRL_GEMM_X6_SMALL=0: f32); "N" operands only (the
-    // transposed staging needs whole 4 x 4 groups per thread)
+    // 64 x 64 tiles with split-bf16 products; "N" operands only (the transposed staging needs whole
+    // 4 x 4 groups per thread).  On since the rollout's projections moved to the decode GEMM
+    // (dgemm.hip): the learn step's mid-sized GEMMs gain (C3 learn -0.2 ... -0.5 ms in 5 of 5 A/B
+    // rounds); round 1 had it off for the decode shapes (rollout 38.7 vs 38.1 ms)
     if constexpr (!TA && !TB && EPI != EPI_DGATE) {
-      if (use_x6() && use_x6_small()) {
+      if (use_x6()) {
         launch<2, 2, 1, 1, 1, TA, TB, EPI, LN, RES, true, true>(a, s);
         done = true;
       }
@@ -1835,11 +1787,6 @@ struct SkinnyPick {
 };
 static SkinnyPick skinny_pick(int N, int Kx) {
   SkinnyPick p;
-  static const bool on = [] {   // XTRL_WGRAD_SKINNY=0: the 64 x 64 GEMM for these too
-    const char* e = getenv("XTRL_WGRAD_SKINNY");
-    return !(e && atoi(e) == 0);
-  }();
-  if (!on) return p;
   auto s_of = [](int x) { return x <= 4 ? 4 : x <= 8 ? 8 : x <= 12 ? 12 : x <= 16 ? 16 : x <= 24 ? 24 : x <= 32 ? 32 : 0; };
   if (Kx <= N && s_of(Kx) && N <= 512) {
     p.tall = true; p.S = s_of(Kx); p.LJ = (N + 255) / 256;
@@ -1933,14 +1880,10 @@ int gemm_wgrad(const float* dY, int ldy, const float* X, int ldx, float* dW, int
   XTRL_REQUIRE(dY && X && dW && M > 0 && N > 0 && K > 0, "gemm_wgrad: bad arguments");
   XTRL_REQUIRE(ldy >= N && ldx >= K && ldw >= K, "gemm_wgrad: leading dims too small");
   XTRL_REQUIRE(!db || beta == 1.f, "gemm_wgrad: the bias gradient accumulates (beta = 1)");
-  // skinny shapes (k_wgrad_skinny): a workgroup per `span` tokens (XTRL_SKINNY_SPAN, default 64; at
-  // most 1024 partials), reduced at once behind any queued split-K partials in ws
+  // skinny shapes (k_wgrad_skinny): a workgroup per `span` tokens (64; at most 1024 partials),
+  // reduced at once behind any queued split-K partials in ws
   if (const SkinnyPick sk = ws ? skinny_pick(N, K + (db ? 1 : 0)) : SkinnyPick{}; sk.S && M >= 64) {
-    static const int sk_span = [] {
-      const char* e = getenv("XTRL_SKINNY_SPAN");
-      return std::max(32, ((e ? atoi(e) : 64) + 31) / 32 * 32);
-    }();
-    int span = std::max(sk_span, (int)(((M + 1023) / 1024 + 31) / 32 * 32));
+    int span = std::max(64, (int)(((M + 1023) / 1024 + 31) / 32 * 32));
     int sp = (M + span - 1) / span;
     const int64_t per = (int64_t)N * K + (db ? N : 0);
     float* w = ws;
@@ -1982,11 +1925,7 @@ int gemm_wgrad(const float* dY, int ldy, const float* X, int ldx, float* dW, int
   const bool big = (int64_t)N * K >= 256 * 256;
   const int tm = big ? 128 : 64;
   const int64_t tiles = (int64_t)((N + tm - 1) / tm) * ((K + tm - 1) / tm);
-  static const int64_t big_target = [] {   // XTRL_WGRAD_TARGET: workgroups of the 128 x 128 launch
-    const char* e = getenv("XTRL_WGRAD_TARGET");
-    return (int64_t)(e ? atoi(e) : 192);
-  }();
-  const int64_t target = big ? big_target : 1024;
+  const int64_t target = big ? 192 : 1024;
   int splits = (int)std::max<int64_t>(1, std::min<int64_t>((target + tiles - 1) / tiles, (M + 255) / 256));
   int kspan = ((M + splits - 1) / splits + 31) / 32 * 32;
   splits = (M + kspan - 1) / kspan;
@@ -2036,11 +1975,7 @@ int gemm_wgrad(const float* dY, int ldy, const float* X, int ldx, float* dW, int
   else if (big) {
     const bool timed = prof && prof->events && *prof->n < prof->cap;
     if (timed) (void)hipEventRecord((hipEvent_t)prof->events[2 * *prof->n], s);
-    static const bool wgrad_ws = [] {   // XTRL_WGRAD_WS=0: register-staged kernel for weight gradients
-      const char* e = getenv("XTRL_WGRAD_WS");
-      return !(e && atoi(e) == 0);
-    }();
-    if (use_x6() && wgrad_ws && ws_ok(a, true, false)) {
+    if (use_x6() && ws_ok(a, true, false)) {
       if (a.K % 32 == 0) launch_ws<true, true, EPI_NONE, false>(a, s);
       else launch_ws<true, true, EPI_NONE, false, 128, 128, true>(a, s);
     }

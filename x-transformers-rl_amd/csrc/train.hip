@@ -918,8 +918,8 @@ inline int ld_ff(const XtrlTrainDesc* D) { return D->ld_ff > 0 ? D->ld_ff : D->f
 // main stream marks its dY ready; the main stream waits for a specific side event before it
 // overwrites a buffer a pending weight gradient still reads (dx, dff, dproj), and for all of them
 // at the end of the backward.  The side stream and its event pool are created once per process
-// (one device per process, grown to the deepest model seen) and hold no data.
-// XTRL_WGRAD_STREAM=0: everything on one stream.
+// (one device per process, grown to the deepest model seen) and hold no data.  If the stream cannot
+// be created, everything runs on one stream.
 struct SideStream {
   hipStream_t s = nullptr;
   std::vector<hipEvent_t> ev;
@@ -928,14 +928,9 @@ struct SideStream {
   // events only order two streams of this device, so they are recorded with a device-scope
   // release instead of the default system-scope fence (the kernels' own end-of-kernel release and
   // start-of-kernel acquire carry the data): the main stream's gap at a fork shrinks, C3 learn
-  // −0.7 ms.  XTRL_FORK_FENCE=0: system scope (the HIP default); 2: no fence at all (A/B only)
+  // −0.7 ms against the HIP default (system scope)
   bool ensure(size_t n) {
-    static const unsigned flags = [] {
-      const char* f = getenv("XTRL_FORK_FENCE");
-      const int v = f ? atoi(f) : 1;
-      return (unsigned)hipEventDisableTiming |
-             (v == 1 ? (unsigned)hipEventReleaseToDevice : v == 2 ? (unsigned)hipEventDisableSystemFence : 0u);
-    }();
+    constexpr unsigned flags = hipEventDisableTiming | hipEventReleaseToDevice;
     while (ok && ev.size() < n) {
       hipEvent_t e = nullptr;
       if (hipEventCreateWithFlags(&e, flags) != hipSuccess) return false;
@@ -947,25 +942,9 @@ struct SideStream {
 SideStream& side_stream() {
   static SideStream S = [] {
     SideStream x;
-    const char* e = getenv("XTRL_WGRAD_STREAM");
-    if (e && atoi(e) == 0) return x;
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
-    // XTRL_WGRAD_CUS=n (experiments): the side stream confined to n CUs, every (CUs / n)-th one
-    const char* cus = getenv("XTRL_WGRAD_CUS");
-    int dev = 0, ncu = 0;
-    if (cus && atoi(cus) > 0 && hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) {
-      const int want = std::min(atoi(cus), ncu), step = std::max(1, ncu / want);
-      std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-      for (int i = 0, n = 0; i < ncu && n < want; i += step, ++n) mask[i / 32] |= 1u << (i % 32);
-      x.ok = hipExtStreamCreateWithCUMask(&x.s, (uint32_t)mask.size(), mask.data()) == hipSuccess;
-      return x;
-    }
-    // XTRL_WGRAD_PRIO=1 (experiments): the side stream at the highest priority instead of the lowest
-    const char* pr = getenv("XTRL_WGRAD_PRIO");
-    x.ok = hipStreamCreateWithPriority(&x.s, hipStreamNonBlocking, (pr && atoi(pr) == 1) ? greatest : least) ==
-           hipSuccess;
+    x.ok = hipStreamCreateWithPriority(&x.s, hipStreamNonBlocking, least) == hipSuccess;
     return x;
   }();
   return S;
@@ -1105,11 +1084,7 @@ int ln_bwd(const Ctx& c, const float* g1, int ldg1, float s1, const float* g2, i
 // LayerNorm folded into the GEMM that produces / consumes its rows (gemm.hip EPI_RES_LN /
 // EPI_LN_BWD): possible when one column tile holds the whole row and every operand is float4
 bool ln_fusable(const XtrlTrainDesc* D) {
-  static const bool on = [] {   // XTRL_FUSED_LN=0: separate LayerNorm launches (A/B experiments)
-    const char* e = getenv("XTRL_FUSED_LN");
-    return !(e && atoi(e) == 0);
-  }();
-  if (!on || D->d % 4 || D->d > 256 || (D->H * D->dh) % 4 || D->ff % 4 || D->in_dim % 4) return false;
+  if (D->d % 4 || D->d > 256 || (D->H * D->dh) % 4 || D->ff % 4 || D->in_dim % 4) return false;
   for (int li = 0; li < D->L; ++li)
     if (D->layers[li].n_qkv % 4) return false;
   return true;
@@ -1300,14 +1275,10 @@ void scatter_rows(const float* src, int lds, const int32_t* inv, int T, int cols
   if (v4) hipLaunchKernelGGL(k_scatter_rows<4>, dim3(blocks(units, 256)), dim3(256), 0, s, src, lds, inv, T, cols, dst, ldd);
   else hipLaunchKernelGGL(k_scatter_rows<1>, dim3(blocks(units, 256)), dim3(256), 0, s, src, lds, inv, T, cols, dst, ldd);
 }
-// the world-model heads run on the valid rows only (XtrlTrainDesc.Tv; XTRL_HEADS_COMPACT=0: every row)
+// the world-model heads run on the valid rows only (XtrlTrainDesc.Tv)
 bool heads_compact(const Ctx& c) {
-  static const bool on = [] {
-    const char* e = getenv("XTRL_HEADS_COMPACT");
-    return !(e && atoi(e) == 0);
-  }();
   const XtrlTrainDesc* D = c.D;
-  return on && D->Tv > 0 && D->Tv < c.T && D->b <= VR_MAXB && D->vrows && D->vinv && D->ewa_v && D->hp_v &&
+  return D->Tv > 0 && D->Tv < c.T && D->b <= VR_MAXB && D->vrows && D->vinv && D->ewa_v && D->hp_v &&
          D->zp_v && D->pred_v && D->d_pred_v && D->dzp_v && D->dewa_v;
 }
 }  // namespace
@@ -1532,26 +1503,17 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
   SideStream& side = side_stream();
   const bool two = side.ok && side.ensure(side_events_needed(D->L));
   Fork F{s, side.s, two ? &side : nullptr};
-  // weight gradients (side stream); their split-K partials are summed by one launch at the end
-  // (XTRL_SPLITK_DEFER=0: a reduce launch after every weight-gradient GEMM)
-  static const bool defer = [] {
-    const char* e = getenv("XTRL_SPLITK_DEFER");
-    return !(e && atoi(e) == 0);
-  }();
   // the LayerNorm d gamma sums of the final norm and the decoder blocks: deferred to one launch after
   // the blocks (nothing else writes the partial workspace until the embeddings), or at each gradient
-  // bucket; XTRL_LN_COLSUM_DEFER=0: a column-sum launch after every LayerNorm-backward GEMM
-  static const bool cs_defer = [] {
-    const char* e = getenv("XTRL_LN_COLSUM_DEFER");
-    return !(e && atoi(e) == 0);
-  }();
+  // bucket
   ColsumQueue csq;
-  if (cs_defer && ln_fusable(D) && D->scratch_per_layer) {
+  if (ln_fusable(D) && D->scratch_per_layer) {
     csq.base = D->part;
     csq.cap = D->part_floats;
   }
+  // weight gradients (side stream); their split-K partials are summed by one launch at the end
   SplitKQueue skq;
-  const Ctx cw{D, two ? side.s : s, T, defer ? &skq : nullptr};
+  const Ctx cw{D, two ? side.s : s, T, &skq};
   // data-parallel gradient buckets: flush the bucket's deferred reductions, then record its events
   int bucket = 0;
   auto bucket_done = [&]() -> int {
@@ -1710,12 +1672,8 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
   // ---- embeddings: dx is d x0.  The deferred split-K sums start now on the side stream, beside the
   // embedding backward, and project_in's small weight gradient runs on the main stream into the
   // workspace behind them (its immediate reduce; the backward's tail was that gradient waiting for its
-  // fork, then the whole flush).  XTRL_WPIN_MAIN=0: on the side stream, before the flush.
-  static const bool wpin_main = [] {
-    const char* e = getenv("XTRL_WPIN_MAIN");
-    return !(e && atoi(e) == 0);
-  }();
-  const bool wpin_on_main = wpin_main && !D->continuous && !D->grad_events && skq.used < D->ws_floats;
+  // fork, then the whole flush).  Otherwise: on the side stream, before the flush.
+  const bool wpin_on_main = !D->continuous && !D->grad_events && skq.used < D->ws_floats;
   if (wpin_on_main) {
     const int64_t used0 = skq.used;
     if ((rc = splitk_flush(skq, cw.s))) return rc;
@@ -1940,11 +1898,7 @@ int dgrad_post_ln2(const Ctx& c, const float* dY, int ldy, const float* W, const
 }
 
 bool ln_fusable_fractal(const XtrlTrainDesc* D) {
-  static const bool on = [] {
-    const char* e = getenv("XTRL_FUSED_LN");
-    return !(e && atoi(e) == 0);
-  }();
-  return on && D->d % 4 == 0 && D->d <= 256 && D->ff % 4 == 0;
+  return D->d % 4 == 0 && D->d <= 256 && D->ff % 4 == 0;
 }
 
 AttnProblem fractal_attn(const Ctx& c, int level) {
@@ -2073,12 +2027,8 @@ int fractal_train_backward(const XtrlTrainDesc* D, const XtrlFractalTrainDesc* F
   SideStream& side = side_stream();
   const bool two = side.ok && side.ensure(fractal_events_needed(Lv));
   Fork Fk{s, side.s, two ? &side : nullptr};
-  static const bool defer = [] {
-    const char* e = getenv("XTRL_SPLITK_DEFER");
-    return !(e && atoi(e) == 0);
-  }();
   SplitKQueue skq;
-  const Ctx cw{D, two ? side.s : s, T, defer ? &skq : nullptr};
+  const Ctx cw{D, two ? side.s : s, T, &skq};
   // data-parallel gradient buckets (FractalPolicyActorCritic.flat_buckets_names): [heads, action
   // embedding, final aggregation], one per level (last to first), [the rest]; each flushes its
   // deferred split-K reductions and records an event on both streams once its gradients are final
@@ -2135,7 +2085,7 @@ int fractal_train_backward(const XtrlTrainDesc* D, const XtrlFractalTrainDesc* F
   if ((rc = bucket_done())) return rc;   // bucket 0: heads, action embedding, final aggregation
   // levels, last to first.  dgn: gradient of g_{l+1} (the final g: cat's last d columns); dxn:
   // gradient of x3_l from level l + 1's input (none for the last level).
-  // the chained post-norm LayerNorm backward epilogue (XTRL_FUSED_LN=0: separate launches)
+  // the chained post-norm LayerNorm backward epilogue (d > 256 or ff % 4: separate launches)
   const bool post2 = ln_fusable_fractal(D);
   const float* dgn = F->dcat + Lv * d;
   int lddgn = ldcat;
@@ -2209,11 +2159,7 @@ int fractal_train_backward(const XtrlTrainDesc* D, const XtrlFractalTrainDesc* F
   // input embedding (x_in,0 = state W_in^T + b_in + le[0]) and global_state_init (g_0 on every row).
   // As the decoder step's backward: the queued split-K sums start on the side stream here and the
   // small input-projection gradient runs on the main stream behind them in the workspace
-  static const bool wpin_main = [] {
-    const char* e = getenv("XTRL_WPIN_MAIN");
-    return !(e && atoi(e) == 0);
-  }();
-  const bool wpin_on_main = wpin_main && !D->grad_events && skq.used < D->ws_floats;
+  const bool wpin_on_main = !D->grad_events && skq.used < D->ws_floats;
   if (wpin_on_main) {
     const int64_t used0 = skq.used;
     if ((rc = splitk_flush(skq, cw.s))) return rc;

@@ -25,7 +25,6 @@ from __future__ import annotations
 
 import copy
 import math
-import os
 from pathlib import Path
 
 import numpy as np
@@ -559,10 +558,9 @@ class Agent(nn.Module):
         self.step += 1
 
     def bucket_allreduce(self):
-        """The overlapped bucketed all-reduce of the fused learn step (None: one process, or
-        XTRL_DP_BUCKETS=0 for one all-reduce after the backward)."""
-        if not dist_.dp_active() or os.environ.get('XTRL_DP_BUCKETS', '1') == '0' \
-                or not hasattr(self.model, 'flat_bucket_ranges') or self.flat.flat.device.type != 'cuda':
+        """The overlapped bucketed all-reduce of the fused learn step (None: one process)."""
+        if not dist_.dp_active() or not hasattr(self.model, 'flat_bucket_ranges') \
+                or self.flat.flat.device.type != 'cuda':
             return None
         bar = getattr(self, '_bar', None)
         if bar is None:

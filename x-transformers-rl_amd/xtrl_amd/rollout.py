@@ -76,7 +76,7 @@ class RolloutEngine:
         # one-launch feed-forward (k_mlp): per 16-row panel, one FF2 partial per 128-wide hidden chunk
         # and the panel's arrival counter (the last chunk workgroup sums the partials and resets it)
         n_chunk = ff // 128 if (ff % 128 == 0 and d % 64 == 0 and d <= 256 and not glu) else 0
-        self.mlp_part = z(((E + 31) // 32) * 32 * n_chunk * d) if n_chunk else None   # (16- or 32-row panels)
+        self.mlp_part = z(((E + 31) // 32) * 32 * n_chunk * d) if n_chunk else None   # (the header's size: E up to 32 rows)
         self.mlp_cnt = z((E + 15) // 16, dt=i32) if n_chunk else None
         self.kv = [(z(E, Hkv, Tmax, dh), z(E, Hkv, Tmax, dh)) for _ in range(c.depth)]
         # decode weights (nn.Linear layouts; the GEMM operands are packed from them, self.wpk)
@@ -378,7 +378,7 @@ class RolloutEngine:
         """The per-episode decode state carried between deploy calls (Agent.forward hiddens)."""
         return [t for kv in self.kv for t in kv] + [self.v1]
 
-    CHUNK = int(os.environ.get('XTRL_ROLLOUT_CHUNK', '32'))   # steps per captured sub-graph
+    CHUNK = 32   # steps per captured sub-graph
 
     @torch.no_grad()
     def run(self, seed, update, episode_of_slot, latent=None, slot_offset=0, slots=None):
