@@ -1,0 +1,182 @@
+"""What the attention GPU tests share (test_gpu_parity.py, test_attn_window_gpu.py, test_attn_gqa_gpu.py,
+test_attn_sink_gpu.py): the one driver of the learn-step attention kernels through the C ABI (attn_lib, which
+reaches every entry-point family: xtrl_attn_fwd / _bwd / _bwd_part and their _win, _gqa and _sink forms), the
+kernel-level problem builder, the fp64 band softmax, the bounds against an fp64 reference (check_ref) and the
+model-level body "rollout, then n learn minibatches against a patched oracle" (rollout_and_learn).  The Learner
+builder and the other model-level bodies are test_gpu_parity's: make_learner, _packed_vs_padded,
+_fused_vs_autograd, deploy_parity.
+
+A plain module that defines no tests, so pytest does not rewrite its asserts: each one carries its message."""
+import contextlib
+import os
+
+import torch
+
+import test_gpu_parity as G
+
+DEV = 'cuda'
+NAMES = ('o', 'lse', 'delta', 'dq', 'dk', 'dv')
+
+
+# ----------------------------------------------------------------------------------------------
+# kernel level
+# ----------------------------------------------------------------------------------------------
+
+
+@contextlib.contextmanager
+def fused_bwd(on):
+    """XTRL_ATTN_FUSED_BWD (read per launch) at 1 / 0 for the launches inside, then as it was."""
+    old = os.environ.get('XTRL_ATTN_FUSED_BWD')
+    os.environ['XTRL_ATTN_FUSED_BWD'] = '1' if on else '0'
+    try:
+        yield
+    finally:
+        if old is None:
+            del os.environ['XTRL_ATTN_FUSED_BWD']
+        else:
+            os.environ['XTRL_ATTN_FUSED_BWD'] = old
+
+
+def attn_lib(q, k, v, lens, do, scale, p, mode, abi, W=None, mem_k=None, mem_v=None, Z=False, seed=3, offset=1, sub=0):
+    """Forward + backward through the C ABI; every output and workspace holds NaN before the calls, so an
+    element no kernel wrote shows.  Returns o, lse, delta, dq, dk, dv (and dmk, dmv at M > 0).
+
+    ``abi``: the entry-point family — 'plain' (xtrl_attn_fwd / xtrl_attn_bwd / xtrl_attn_bwd_part; no window),
+    'win' (their _win forms; ``W`` None: the plain ones), 'gqa' (_gqa: k, v [b][Hkv][n][dh]; ``W`` None: window
+    0, none) or 'sink' (_sink: GQA and window as 'gqa', plus mem_k, mem_v [Hkv][M][dh] — None: M = 0, null
+    pointers — and the zero key ``Z``).
+    ``mode``: 'two' (XTRL_ATTN_FUSED_BWD=0: the dK/dV + dQ kernel pair), 'fused' (=1 without a workspace: one
+    launch for n <= 128 at Hkv = H; Hkv < H has no fused form and runs the pair) or 'part' (=1 through
+    xtrl_attn_bwd_part*: the long-episode backward with the dQ partial workspace)."""
+    from xtrl_amd import _lib as L
+    lib = L.lib()
+    b, H, n, dh = q.shape
+    Hkv = k.shape[1]
+    M = 0 if mem_k is None else mem_k.shape[1]
+    assert abi in ('plain', 'win', 'gqa', 'sink') and mode in ('two', 'fused', 'part'), (abi, mode)
+    assert abi != 'plain' or W is None, f"abi 'plain' takes no window, W = {W}"
+    assert abi in ('gqa', 'sink') or Hkv == H, f'abi {abi!r} takes k, v with all H = {H} heads, not {Hkv}'
+    assert abi == 'sink' or (M == 0 and not Z), f'abi {abi!r} takes no sinks (M = {M}, Z = {Z})'
+    suffix = '' if abi == 'plain' or (abi == 'win' and W is None) else '_' + abi
+    nan = lambda *s: torch.full(s, float('nan'), device=DEV)   # noqa: E731
+    o, dq, dk, dv = nan(*q.shape), nan(*q.shape), nan(*k.shape), nan(*v.shape)
+    lse, delta = nan(b, H, n), nan(b, H, n)
+    res = dict(o=o, lse=lse, delta=delta, dq=dq, dk=dk, dv=dv)
+    # the arguments after the pointers: b, H, [Hkv,] n, dh, scale, p, seed, offset, sub, [window,] [M, Z,] stream
+    tail = (b, H) + ((Hkv,) if abi in ('gqa', 'sink') else ()) + (n, dh, scale, p, seed, offset, sub) \
+        + ((int(W or 0),) if suffix else ()) + ((M, int(Z)) if abi == 'sink' else ()) + (L.stream(),)
+    fwd_sink = bwd_sink = ()
+    if abi == 'sink':
+        nws = int(lib.xtrl_attn_sink_ws_floats(b, H, M, dh))
+        dmk, dmv, ws = (nan(Hkv, M, dh), nan(Hkv, M, dh), nan(nws)) if M else (None, None, None)
+        fwd_sink = (L.ptr(mem_k), L.ptr(mem_v))
+        bwd_sink = fwd_sink + (L.ptr(dmk), L.ptr(dmv), L.ptr(ws), nws)
+        if M:
+            res.update(dmk=dmk, dmv=dmv)
+    io = tuple(L.ptr(t) for t in (q, k, v, lens, o, lse))
+    L.check(getattr(lib, 'xtrl_attn_fwd' + suffix)(*io, *fwd_sink, *tail), 'attn_fwd' + suffix)
+    grads = tuple(L.ptr(t) for t in (do, dq, dk, dv, delta))
+    with fused_bwd(mode != 'two'):
+        if mode == 'part':
+            nf = int(lib.xtrl_attn_bwd_part_floats(b, H, n, dh))
+            part = nan(nf)
+            L.check(getattr(lib, 'xtrl_attn_bwd_part' + suffix)(*io, *grads, L.ptr(part), nf, *bwd_sink, *tail),
+                    'attn_bwd_part' + suffix)
+        else:
+            L.check(getattr(lib, 'xtrl_attn_bwd' + suffix)(*io, *grads, *bwd_sink, *tail), 'attn_bwd' + suffix)
+    torch.cuda.synchronize()
+    return res
+
+
+def ragged_lens(g, b, n):
+    """lens[0] = n, one episode of a single step, the others random."""
+    lens = torch.randint(1, n + 1, (b,), generator=g).to(torch.int32)
+    lens[0] = n
+    lens[b - 1] = 1
+    return lens.to(DEV)
+
+
+def problem(b, H, n, dh, seed, Hkv=None, M=0):
+    """q, k, v, do [b][H][n][dh] and ragged lens from one generator; ``Hkv``: k, v cut to their first Hkv heads;
+    ``M`` > 0: mem_k, mem_v [Hkv][M][dh] (from a generator of their own, seed + 1000) follow in the tuple."""
+    g = torch.Generator().manual_seed(seed)
+    q, k, v, do = (torch.randn(b, H, n, dh, generator=g).to(DEV) for _ in range(4))
+    lens = ragged_lens(g, b, n)
+    if Hkv is not None:
+        k, v = k[:, :Hkv].contiguous(), v[:, :Hkv].contiguous()
+    if not M:
+        return q, k, v, do, lens
+    g = torch.Generator().manual_seed(seed + 1000)
+    mem_k, mem_v = (torch.randn(H if Hkv is None else Hkv, M, dh, generator=g).to(DEV) for _ in range(2))
+    return q, k, v, do, lens, mem_k, mem_v
+
+
+def modes_of(n, dh):
+    """The backward modes that exist for a shape: the pair always; at dh = 16 the partial-workspace form,
+    and for n <= 128 the fused dispatch."""
+    return ['two'] + (['part'] if dh == 16 else []) + (['fused'] if dh == 16 and n <= 128 else [])
+
+
+def band_mask(n, lens, W):
+    """[b][1][n][n]: key j visible to query i iff j <= i, i - j <= W and j < len."""
+    i = torch.arange(n, device=lens.device)
+    dist = i[:, None] - i[None, :]
+    return ((dist >= 0) & (dist <= W))[None, None] & (i[None, None, None, :] < lens.long()[:, None, None, None])
+
+
+def attn_win_ref(q, k, v, lens, scale, W, keep=None):
+    """G.attn_ref (dense softmax, masked scores filled with the finite -max as x-transformers does)
+    plus the band mask.  A row whose band holds no valid key — a padded row i >= len + W — therefore
+    attends all n key positions uniformly and passes no gradient to its scores (without a window no
+    row of an episode with a valid key is empty, so attn_ref never meets one)."""
+    n = q.shape[2]
+    mask = band_mask(n, lens, W)
+    s = torch.einsum('bhid,bhjd->bhij', q, k) * scale
+    p = s.masked_fill(~mask, -torch.finfo(s.dtype).max).softmax(-1)
+    if keep is not None:
+        p = p * keep
+    return torch.einsum('bhij,bhjd->bhid', p, v)
+
+
+def check_ref(res, ref):
+    """attn_lib's results against an fp64 reference (a dict of CPU tensors): o — and lse and the row sum
+    L = exp(lse), where the reference has lse — within 1e-5 + 1e-5, every gradient of the reference (dq, dk, dv;
+    dmk, dmv) within 1e-4 + 1e-5."""
+    grads = [name for name in ref if name.startswith('d')]
+    assert 'o' in ref and set(grads) >= {'dq', 'dk', 'dv'} and set(ref) <= {'o', 'lse', *grads}, sorted(ref)
+    G.tol(res['o'], ref['o'], 1e-5, 1e-5)
+    if 'lse' in ref:
+        G.tol(res['lse'], ref['lse'], 1e-5, 1e-5)
+        G.tol(res['lse'].exp(), ref['lse'].exp(), 1e-5, 1e-5)
+    for name in grads:
+        G.tol(res[name], ref[name], 1e-4, 1e-5)
+
+
+# ----------------------------------------------------------------------------------------------
+# model level
+# ----------------------------------------------------------------------------------------------
+
+
+def rollout_and_learn(monkeypatch, install, T, minibatches, packed=False, checks=None, **learner_kw):
+    """Rollout (G.compare_rollout: actions, lengths, rewards bit-exact; log-probs and logits within 1e-4) and
+    ``minibatches`` learn minibatches (G._learn_parity: loss within 1e-4 relative, every gradient within 1e-4 of
+    the gradient scale) against a patched oracle.  ``install(monkeypatch)`` puts the feature's Attention over the
+    frozen oracle's before anything is built; ``learner_kw``: G.make_learner's keywords; ``packed``: the packed
+    learn step, with the per-token critic reduction on both sides; ``checks(learner, env, oracle)``: the
+    feature's own assertions, made after the rollout.  Returns (learner, lens, seen)."""
+    install(monkeypatch)
+    if packed:
+        learner_kw['agent_extra'] = dict(learner_kw.get('agent_extra') or {}, hl_reduction_mean=False, packed_learn=True)
+    learner, env, oracle = G.make_learner(T=T, **learner_kw)
+    traj, lens, genes, cum = learner.rollout_device(env, 0, T)
+    torch.cuda.synchronize()
+    if checks is not None:
+        checks(learner, env, oracle)
+    episodes, _ = oracle.rollout(0)
+    G.compare_rollout(traj, lens, episodes)
+    seen = []
+    if minibatches:
+        with G._hl_reduction(not packed):
+            seen = G._learn_parity(learner, oracle, traj, lens, genes, learner.fitness(cum, genes), minibatches,
+                                   packed=packed)
+    return learner, lens, seen

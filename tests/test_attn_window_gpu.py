@@ -2,15 +2,16 @@
 0 <= i - j <= W and j < len) on the MI355X: the windowed learn-step kernels through the C ABI against
 an fp64 dense reference, and rollout / learn step / deploy against the windowed oracle
 (test_attn_window_cpu.windowed_forward installed over the frozen oracle's Attention.forward)."""
-import os
+import functools
 
 import pytest
 import torch
 
-from oracle import ref_port as R
 from oracle import thirdparty as tp
 
+import attn_harness as AH
 import test_gpu_parity as G
+from attn_harness import attn_win_ref, check_ref, problem
 from test_attn_window_cpu import windowed_forward
 from test_gpu_parity import tol
 
@@ -22,101 +23,22 @@ DEV = 'cuda'
 # kernel level
 # ----------------------------------------------------------------------------------------------
 
-
-def band_mask(n, lens, W):
-    """[b][1][n][n]: key j visible to query i iff j <= i, i - j <= W and j < len."""
-    i = torch.arange(n, device=lens.device)
-    dist = i[:, None] - i[None, :]
-    return ((dist >= 0) & (dist <= W))[None, None] & (i[None, None, None, :] < lens.long()[:, None, None, None])
-
-
-def attn_win_ref(q, k, v, lens, scale, W, keep=None):
-    """G.attn_ref (dense softmax, masked scores filled with the finite -max as x-transformers does)
-    plus the band mask.  A row whose band holds no valid key — a padded row i >= len + W — therefore
-    attends all n key positions uniformly and passes no gradient to its scores (without a window no
-    row of an episode with a valid key is empty, so attn_ref never meets one)."""
-    n = q.shape[2]
-    mask = band_mask(n, lens, W)
-    s = torch.einsum('bhid,bhjd->bhij', q, k) * scale
-    p = s.masked_fill(~mask, -torch.finfo(s.dtype).max).softmax(-1)
-    if keep is not None:
-        p = p * keep
-    return torch.einsum('bhij,bhjd->bhid', p, v)
-
-
-def ragged_lens(g, b, n):
-    """lens[0] = n, one episode of a single step, the others random."""
-    lens = torch.randint(1, n + 1, (b,), generator=g).to(torch.int32)
-    lens[0] = n
-    lens[b - 1] = 1
-    return lens.to(DEV)
-
-
-def win_lib(q, k, v, lens, do, scale, p, W, mode, seed=3, offset=1, sub=0):
-    """Forward + backward through the C ABI.  ``W`` None: the unwindowed entry points (xtrl_attn_fwd /
-    xtrl_attn_bwd / xtrl_attn_bwd_part), else their _win forms.  ``mode``: 'two' (the dK/dV + dQ
-    kernel pair, XTRL_ATTN_FUSED_BWD=0), 'fused' (=1: one launch for n <= 128) or 'part' (the long-episode
-    backward with a dQ partial workspace)."""
-    from xtrl_amd import _lib as L
-    lib = L.lib()
-    b, H, n, dh = q.shape
-    o = torch.empty_like(q)
-    dq, dk, dv = (torch.full_like(q, float('nan')) for _ in range(3))
-    lse, delta = (torch.empty(b, H, n, device=DEV) for _ in range(2))
-    win = () if W is None else (int(W),)
-    fwd = lib.xtrl_attn_fwd if W is None else lib.xtrl_attn_fwd_win
-    L.check(fwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), b, H, n, dh, scale, p, seed, offset, sub,
-                *win, L.stream()), 'attn_fwd')
-    old = os.environ.get('XTRL_ATTN_FUSED_BWD')
-    os.environ['XTRL_ATTN_FUSED_BWD'] = '0' if mode == 'two' else '1'
-    try:
-        if mode == 'part':
-            nf = int(lib.xtrl_attn_bwd_part_floats(b, H, n, dh))
-            part = torch.full((nf,), float('nan'), device=DEV)
-            bwd = lib.xtrl_attn_bwd_part if W is None else lib.xtrl_attn_bwd_part_win
-            L.check(bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do), L.ptr(dq), L.ptr(dk),
-                        L.ptr(dv), L.ptr(delta), L.ptr(part), nf, b, H, n, dh, scale, p, seed, offset, sub, *win,
-                        L.stream()), 'attn_bwd_part')
-        else:
-            bwd = lib.xtrl_attn_bwd if W is None else lib.xtrl_attn_bwd_win
-            L.check(bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do), L.ptr(dq), L.ptr(dk),
-                        L.ptr(dv), L.ptr(delta), b, H, n, dh, scale, p, seed, offset, sub, *win, L.stream()), 'attn_bwd')
-    finally:
-        if old is None:
-            del os.environ['XTRL_ATTN_FUSED_BWD']
-        else:
-            os.environ['XTRL_ATTN_FUSED_BWD'] = old
-    torch.cuda.synchronize()
-    return dict(o=o, lse=lse, delta=delta, dq=dq, dk=dk, dv=dv)
-
-
-def problem(b, H, n, dh, seed):
-    g = torch.Generator().manual_seed(seed)
-    q, k, v, do = (torch.randn(b, H, n, dh, generator=g).to(DEV) for _ in range(4))
-    return q, k, v, do, ragged_lens(g, b, n)
-
-
+# W=None: the unwindowed entry points (xtrl_attn_fwd / xtrl_attn_bwd / xtrl_attn_bwd_part), else their _win forms
+win_lib = functools.partial(AH.attn_lib, abi='win')
 _REF = {}
 
 
 def fp64_ref(b, H, n, dh, W):
-    """(o, dq, dk, dv) of the fp64 reference on problem(b, H, n, dh, n + dh + W); computed once."""
+    """o, dq, dk, dv of the fp64 reference on problem(b, H, n, dh, n + dh + W); computed once."""
     key = (b, H, n, dh, W)
     if key not in _REF:
         q, k, v, do, lens = problem(b, H, n, dh, n + dh + W)
         qd, kd, vd = (t.double().requires_grad_() for t in (q, k, v))
         ref = attn_win_ref(qd, kd, vd, lens, dh ** -0.5, W)
         (ref * do.double()).sum().backward()
-        _REF[key] = tuple(t.detach().cpu() for t in (ref, qd.grad, kd.grad, vd.grad))
+        out = dict(o=ref, dq=qd.grad, dk=kd.grad, dv=vd.grad)
+        _REF[key] = {name: t.detach().cpu() for name, t in out.items()}
     return _REF[key]
-
-
-def check_fp64(res, b, H, n, dh, W):
-    o, dq, dk, dv = fp64_ref(b, H, n, dh, W)
-    tol(res['o'], o, 1e-5, 1e-5)
-    tol(res['dq'], dq, 1e-4, 1e-5)
-    tol(res['dk'], dk, 1e-4, 1e-5)
-    tol(res['dv'], dv, 1e-4, 1e-5)
 
 
 @pytest.mark.parametrize('b,H,n,dh,W', [(3, 4, 37, 16, 5), (2, 2, 70, 16, 1), (2, 2, 130, 16, 10), (2, 2, 200, 16, 63),
@@ -127,9 +49,9 @@ def test_window_forward_and_two_kernel_backward(b, H, n, dh, W):
     through it) and query tile 2 skips key tile 0, whose workgroup no longer stores D for it;
     W = 63 / 64 / 65: bands ending on, at and past a tile edge."""
     q, k, v, do, lens = problem(b, H, n, dh, n + dh + W)
-    res = win_lib(q, k, v, lens, do, dh ** -0.5, 0., W, 'two')
+    res = win_lib(q, k, v, lens, do, dh ** -0.5, 0., 'two', W=W)
     assert all(torch.isfinite(t).all() for t in res.values())
-    check_fp64(res, b, H, n, dh, W)
+    check_ref(res, fp64_ref(b, H, n, dh, W))
 
 
 @pytest.mark.parametrize('W', [10, 64])
@@ -141,16 +63,16 @@ def test_window_fused_backward_matches_two_kernel(W, p):
     tile 1) are masked."""
     b, H, n, dh = 4, 4, 128, 16
     q, k, v, do, lens = problem(b, H, n, dh, n + dh + W)
-    two = win_lib(q, k, v, lens, do, dh ** -0.5, p, W, 'two')
-    fus = win_lib(q, k, v, lens, do, dh ** -0.5, p, W, 'fused')
+    two = win_lib(q, k, v, lens, do, dh ** -0.5, p, 'two', W=W)
+    fus = win_lib(q, k, v, lens, do, dh ** -0.5, p, 'fused', W=W)
     for name in ('o', 'lse', 'delta', 'dv', 'dk', 'dq'):
         d = (two[name] - fus[name]).abs()
         print(name, 'max |diff|', float(d.max()), '#differing', int((d > 0).sum()))
     for name in ('o', 'lse', 'delta', 'dv', 'dk', 'dq'):
         assert torch.equal(two[name], fus[name]), name
     if p == 0.:
-        check_fp64(fus, b, H, n, dh, W)
-        check_fp64(two, b, H, n, dh, W)
+        check_ref(fus, fp64_ref(b, H, n, dh, W))
+        check_ref(two, fp64_ref(b, H, n, dh, W))
 
 
 @pytest.mark.parametrize('b,H,n,W', [(3, 4, 257, 10), (2, 4, 430, 64), (2, 4, 500, 100), (3, 2, 500, 300)])
@@ -163,8 +85,8 @@ def test_window_long_backward_dq_folded(b, H, n, W):
     tile wrote shows."""
     dh = 16
     q, k, v, do, lens = problem(b, H, n, dh, n + dh + W)
-    two = win_lib(q, k, v, lens, do, dh ** -0.5, 0.25, W, 'two')
-    part = win_lib(q, k, v, lens, do, dh ** -0.5, 0.25, W, 'part')
+    two = win_lib(q, k, v, lens, do, dh ** -0.5, 0.25, 'two', W=W)
+    part = win_lib(q, k, v, lens, do, dh ** -0.5, 0.25, 'part', W=W)
     assert torch.equal(part['dv'], two['dv']) and torch.equal(part['dk'], two['dk'])
     assert torch.equal(part['delta'], two['delta'])
     assert torch.isfinite(part['dq']).all()
@@ -178,8 +100,8 @@ def test_window_long_backward_dq_folded(b, H, n, W):
     print('dq err', err, 'scale', scale)
     assert err <= 2e-6 * scale, (err, scale)
     assert int((~sole).sum()) > 0
-    res = win_lib(q, k, v, lens, do, dh ** -0.5, 0., W, 'part')
-    check_fp64(res, b, H, n, dh, W)
+    res = win_lib(q, k, v, lens, do, dh ** -0.5, 0., 'part', W=W)
+    check_ref(res, fp64_ref(b, H, n, dh, W))
 
 
 @pytest.mark.parametrize('b,H,n,mode', [(4, 4, 128, 'two'), (4, 4, 128, 'fused'), (2, 4, 430, 'part')])
@@ -188,9 +110,9 @@ def test_window_covering_every_key_is_bit_identical_to_no_window(b, H, n, mode):
     bit at p = 0.25 — the dropout stream (keyed by absolute i, j), the summation orders and the move of
     D to the diagonal workgroups leave today's results unchanged."""
     q, k, v, do, lens = problem(b, H, n, 16, n)
-    base = win_lib(q, k, v, lens, do, 0.25, 0.25, None, mode)
+    base = win_lib(q, k, v, lens, do, 0.25, 0.25, mode, W=None)
     for W in (n - 1, 4 * n):
-        res = win_lib(q, k, v, lens, do, 0.25, 0.25, W, mode)
+        res = win_lib(q, k, v, lens, do, 0.25, 0.25, mode, W=W)
         for name in ('o', 'lse', 'delta', 'dv', 'dk', 'dq'):
             assert torch.equal(res[name], base[name]), (W, name)
 
@@ -225,51 +147,16 @@ def test_window_dropout_mask_is_host_philox_stream():
 # ----------------------------------------------------------------------------------------------
 
 
-def make_win_learner(W, depth=2, gates=True, T=24, episodes=6, batch=3, seed=3, hazard=5, mode='lander', dim=48,
-                     agent_extra=None, with_key=True):
-    """Learner with world_model['attn_max_attend_past'] = W, the device Sim and the oracle on the same
-    weights (G.make_learner's construction; its option map has no entry for the window, which the
-    oracle takes from the patched Attention.forward instead)."""
-    from xtrl_amd import Learner, SynthVecSim
-    S, A = 8, 4
-    torch.manual_seed(seed)
-    wm = dict(attn_dim_head=16, heads=4, depth=depth)
-    if gates:
-        wm.update(attn_gate_values=True, add_value_residual=True, learned_value_residual_mix=True)
-    if with_key:
-        wm['attn_max_attend_past'] = W
-    gp = dict(dim=8, num_genes_per_island=3, num_selected=2, tournament_size=2)
-    learner = Learner(state_dim=S, num_actions=A, reward_range=(-2., 2.), world_model=wm, max_timesteps=T,
-                      batch_size=batch, num_episodes_per_update=episodes, evolutionary=False, latent_gene_pool=gp,
-                      agent_kwargs=dict(dropout=0., seed=seed, hidden_dim=dim, reward_dropout=0.5, **(agent_extra or {})),
-                      use_graph=False)
-    with torch.no_grad():   # non-trivial gate / mix weights (their init is constant)
-        g = torch.Generator().manual_seed(seed + 1)
-        for name, p in learner.agent.model.named_parameters():
-            if 'to_v_gate' in name or 'to_value_residual_mix' in name:
-                p.copy_((torch.randn(p.shape, generator=g) * 0.3).to(p.device))
-        learner.agent.ema_flat.copy_(learner.agent.flat.flat)
-    env = SynthVecSim(S, A, mode, hazard_log2=hazard)
-    c = R.LearnerConfig(S, A, (-2., 2.), dim=dim, depth=depth, gate_values=gates, value_residual=gates,
-                        learned_mix=gates, max_timesteps=T, batch_size=batch, num_episodes_per_update=episodes,
-                        sim_mode=mode, hazard_log2=hazard, seed=seed, reward_dropout=0.5, gene_pool=gp)
-    sd = {k: v.detach().cpu() for k, v in learner.agent.model.state_dict().items()}
-    oracle = R.OracleLearner(c, init_state_dict=sd)
-    return learner, env, oracle
+LEARNER = dict(episodes=6, batch=3, hazard=5)   # this file's G.make_learner defaults, with T = 24
 
 
 def rollout_and_learn(monkeypatch, W, T, minibatches, **kw):
-    monkeypatch.setattr(tp.Attention, 'forward', windowed_forward(W))
-    learner, env, oracle = make_win_learner(W, T=T, **kw)
-    assert learner.agent.cfg.attn_window == W
-    traj, lens, genes, cum = learner.rollout_device(env, 0, T)
-    torch.cuda.synchronize()
-    episodes, _ = oracle.rollout(0)
-    G.compare_rollout(traj, lens, episodes)
-    seen = []
-    if minibatches:
-        seen = G._learn_parity(learner, oracle, traj, lens, genes, learner.fitness(cum, genes), minibatches)
-    return learner, lens, seen
+    """attn_harness.rollout_and_learn against the windowed oracle; the Learner's descriptor must carry W."""
+    def checks(learner, env, oracle):
+        assert learner.agent.cfg.attn_window == W
+
+    return AH.rollout_and_learn(monkeypatch, lambda mp: mp.setattr(tp.Attention, 'forward', windowed_forward(W)), T,
+                                minibatches, checks=checks, window=W, **{**LEARNER, **kw})
 
 
 @pytest.mark.parametrize('rows', ['1', '0'])
@@ -314,75 +201,22 @@ def test_window_long_episode_learn_matches_oracle(monkeypatch):
 def test_window_packed_learn_matches_padded_step():
     """packed_learn (per-episode row ranges) with W = 9 at T = 70 against the padded step: the bounds
     of test_packed_learn_matches_padded_step."""
-    res = {}
-    for packed in (False, True):
-        learner, env, _ = make_win_learner(9, depth=2, gates=True, T=70, episodes=8, batch=8, seed=5, hazard=5, dim=64,
-                                           agent_extra=dict(hl_reduction_mean=False, packed_learn=packed))
-        agent = learner.agent
-        traj, lens, genes, cum = learner.rollout_device(env, 0, 70)
-        res[packed] = G._first_minibatch_state(agent, traj, lens, genes, learner.fitness(cum, genes))
-        res[packed]['lens'] = lens.cpu()
-    a, b = res[True], res[False]
-    assert torch.equal(a['lens'], b['lens']) and torch.equal(a['idx'], b['idx'])
-    lens_mb = a['lens'][a['idx']].clamp(max=a['n'])
-    assert lens_mb.min() < a['n'] and a['n'] > 64    # padding present; two key tiles
-    valid = (torch.arange(a['n'])[None, :] < lens_mb[:, None]).to(a['raw'].device)
-    assert (a['raw'][~valid] == 0).all() and (a['values'][~valid] == 0).all()
-    for k in ('raw', 'values'):
-        x, y = a[k][valid], b[k][valid]
-        assert float((x - y).abs().max()) <= 1e-4 * float(y.abs().max()) + 1e-6, k
-    assert abs(a['loss'] - b['loss']) <= 1e-5 * abs(b['loss']) + 1e-7, (a['loss'], b['loss'])
-    bad = []
-    for name, (o0, o1) in learner.agent.flat.index.items():
-        g0, g1 = a['grad'][o0:o1], b['grad'][o0:o1]
-        own = float(g1.abs().max())
-        if float((g0 - g1).abs().max()) > 1e-4 * own + 1e-7:
-            bad.append((name, float((g0 - g1).abs().max()), own))
-    assert not bad, bad
+    a = G._packed_vs_padded(False, True, 70, 64, False, None, window=9)
+    assert a['n'] > 64    # two key tiles
 
 
 def test_window_fused_step_matches_reference_mode_autograd():
     """The hand-scheduled learn step against the reference-mode autograd step (ops.attention with the
     window) at T = 70, W = 9, dropout 0.25: the bounds of test_fused_train_step_matches_autograd."""
-    learner, env, _ = make_win_learner(9, depth=2, gates=True, T=70, episodes=8, batch=4, seed=9, hazard=5, dim=64)
-    agent = learner.agent
-    agent.cfg.dropout = 0.25
-    agent.model.cfg.dropout = 0.25
-    traj, lens, genes, cum = learner.rollout_device(env, 0, 70)
-    fit = learner.fitness(cum, genes)
-    agent.fused_learn = True
-    a = G._first_minibatch(agent, traj, lens, genes, fit)
-    agent.fused_learn = False
-    b = G._first_minibatch(agent, traj, lens, genes, fit)
-    assert abs(a['loss'] - b['loss']) <= 1e-5 * abs(b['loss']) + 1e-6, (a['loss'], b['loss'])
-    scale = float(b['grad'].abs().max())
-    for name, (s, e) in agent.flat.index.items():
-        err = float((a['grad'][s:e] - b['grad'][s:e]).abs().max())
-        assert err <= 1e-4 * scale + 1e-7, (name, err, scale)
+    G._fused_vs_autograd(False, False, True, 0.25, 70, depth=2, episodes=8, batch=4, hazard=5, dim=64, window=9)
 
 
 def test_window_deploy_forward_matches_oracle_cached_decode(monkeypatch):
     """Agent.forward (the deploy engine's descriptor carries the window) over 12 steps with W = 4
     against the windowed oracle's cached decode."""
     monkeypatch.setattr(tp.Attention, 'forward', windowed_forward(4))
-    learner, env, oracle = make_win_learner(4, depth=2, gates=True, T=24)
-    agent = learner.agent
-    agent.rs_mean.copy_(torch.linspace(-0.5, 0.5, 9))
-    agent.rs_var.copy_(torch.linspace(0.5, 2., 9))
-    rs = R.RSNormState(9)
-    rs.mean, rs.var = agent.rs_mean.cpu().clone(), agent.rs_var.cpu().clone()
-    m = oracle.model
-    m.eval()
-    g = torch.Generator().manual_seed(2)
-    hiddens, cache = None, None
-    for t in range(12):
-        s = torch.randn(8, generator=g)
-        reward = None if t % 2 == 0 else float(torch.randn((), generator=g))
-        raw, hiddens = agent(s.numpy(), reward=reward, hiddens=hiddens)
-        swr = rs.apply(torch.cat((s, torch.tensor([0. if reward is None else reward]))))
-        with torch.no_grad():
-            r, _, _, _, cache = m(swr[:-1].reshape(1, 1, -1), rewards=None if reward is None else swr[-1], cache=cache)
-        tol(raw, r.reshape(-1), 1e-4, 1e-5)
+    learner, env, oracle = G.make_learner(window=4, T=24, **LEARNER)
+    G.deploy_parity(learner, oracle, 12)
 
 
 def test_window_none_leaves_the_rollout_unchanged():
@@ -390,7 +224,7 @@ def test_window_none_leaves_the_rollout_unchanged():
     without the key."""
     out = []
     for with_key in (True, False):
-        learner, env, _ = make_win_learner(None, T=24, with_key=with_key)
+        learner, env, _ = G.make_learner(window_key=with_key, T=24, **LEARNER)
         assert learner.agent.cfg.attn_window == 0
         traj, lens, _, _ = learner.rollout_device(env, 0, 24)
         torch.cuda.synchronize()

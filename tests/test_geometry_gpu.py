@@ -188,23 +188,7 @@ def test_deploy_forward_matches_oracle_cached_decode(cid):
     decode, as test_gpu_parity.test_deploy_forward_matches_oracle_cached_decode."""
     c = GC.BY_ID[cid]
     learner, env, oracle = G.make_learner(**c.learner_kwargs())
-    agent, S = learner.agent, c.S
-    agent.rs_mean.copy_(torch.linspace(-0.5, 0.5, S + 1))
-    agent.rs_var.copy_(torch.linspace(0.5, 2., S + 1))
-    rs = R.RSNormState(S + 1)
-    rs.mean, rs.var = agent.rs_mean.cpu().clone(), agent.rs_var.cpu().clone()
-    m = oracle.model
-    m.eval()
-    g = torch.Generator().manual_seed(2)
-    hiddens, cache = None, None
-    for t in range(6):
-        s = torch.randn(S, generator=g)
-        reward = None if t % 2 == 0 else float(torch.randn((), generator=g))
-        raw, hiddens = agent(s.numpy(), reward=reward, hiddens=hiddens)
-        swr = rs.apply(torch.cat((s, torch.tensor([0. if reward is None else reward]))))
-        with torch.no_grad():
-            r, _, _, _, cache = m(swr[:-1].reshape(1, 1, -1), rewards=None if reward is None else swr[-1], cache=cache)
-        tol(raw, r.reshape(-1), 1e-4, 1e-5)
+    G.deploy_parity(learner, oracle, 6, S=c.S)
 
 
 # ---- the fractal policy body at H = 2, dh = 32, d = 64, S = 3, A = 5, two levels ------------------------------

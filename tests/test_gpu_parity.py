@@ -17,6 +17,8 @@ from oracle import fractal_ref as FR
 from oracle import ref_port as R
 from oracle import thirdparty as tp
 
+import attn_harness as AH
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 
@@ -311,42 +313,12 @@ def test_attention_fwd_bwd(b, H, n, dh):
     tol(kf.grad, kd.grad, 1e-4, 1e-5)
     tol(vf.grad, vd.grad, 1e-4, 1e-5)
     if dh != 16 and n > 128:
-        res = _attn_bwd_lib(q, k, v, lens, do, scale, 0., False, nan_fill=True)
+        res = AH.attn_lib(q, k, v, lens, do, scale, 0., 'two', 'plain')
         for name, t in res.items():
             assert torch.isfinite(t).all(), name
         tol(res['o'], ref, 1e-5, 1e-5)
         for name, r in (('dq', qd.grad), ('dk', kd.grad), ('dv', vd.grad)):
             tol(res[name], r, 1e-4, 1e-5)
-
-
-def _attn_bwd_lib(q, k, v, lens, do, scale, p, fused, seed=3, offset=1, sub=0, nan_fill=False):
-    """xtrl_attn_fwd + xtrl_attn_bwd through the C ABI, the backward as the fused one-launch kernel
-    (XTRL_ATTN_FUSED_BWD=1, read per launch) or the dK/dV + dQ kernel pair.  ``nan_fill``: every output
-    holds NaN before the calls."""
-    import os
-    from xtrl_amd import _lib as L
-    lib = L.lib()
-    b, H, n, dh = q.shape
-    o, dq, dk, dv = (torch.empty_like(q) for _ in range(4))
-    lse, delta = (torch.empty(b, H, n, device=DEV) for _ in range(2))
-    if nan_fill:
-        for t in (o, dq, dk, dv, lse, delta):
-            t.fill_(float('nan'))
-    L.check(lib.xtrl_attn_fwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), b, H, n, dh, scale, p,
-                              seed, offset, sub, L.stream()), 'attn_fwd')
-    old = os.environ.get('XTRL_ATTN_FUSED_BWD')
-    os.environ['XTRL_ATTN_FUSED_BWD'] = '1' if fused else '0'
-    try:
-        L.check(lib.xtrl_attn_bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do), L.ptr(dq),
-                                  L.ptr(dk), L.ptr(dv), L.ptr(delta), b, H, n, dh, scale, p, seed, offset, sub,
-                                  L.stream()), 'attn_bwd')
-    finally:
-        if old is None:
-            del os.environ['XTRL_ATTN_FUSED_BWD']
-        else:
-            os.environ['XTRL_ATTN_FUSED_BWD'] = old
-    torch.cuda.synchronize()
-    return dict(o=o, lse=lse, delta=delta, dq=dq, dk=dk, dv=dv)
 
 
 @pytest.mark.parametrize('b,H,n,p', [(3, 4, 37, 0.), (4, 4, 128, 0.), (4, 4, 128, 0.25), (2, 2, 10, 0.25),
@@ -361,8 +333,8 @@ def test_attention_fused_backward_matches_two_kernel(b, H, n, p):
     lens = torch.randint(1, n + 1, (b,), generator=g).to(torch.int32)
     lens[0] = n
     lens = lens.to(DEV)
-    two = _attn_bwd_lib(q, k, v, lens, do, 0.25, p, False)
-    fus = _attn_bwd_lib(q, k, v, lens, do, 0.25, p, True)
+    two = AH.attn_lib(q, k, v, lens, do, 0.25, p, 'two', 'plain')
+    fus = AH.attn_lib(q, k, v, lens, do, 0.25, p, 'fused', 'plain')
     report = {}
     for name in ('o', 'lse', 'delta', 'dv', 'dk', 'dq'):
         d = (two[name] - fus[name]).abs()
@@ -388,7 +360,7 @@ def test_attention_long_backward_dq_folded_matches_two_kernel(b, H, n, p):
     if b > 2:
         lens[2] = 40
     lens = lens.to(DEV)
-    two = _attn_bwd_lib(q, k, v, lens, do, 0.25, p, False)
+    two = AH.attn_lib(q, k, v, lens, do, 0.25, p, 'two', 'plain')
     lib = L.lib()
     nf = int(lib.xtrl_attn_bwd_part_floats(b, H, n, 16))
     assert nf == -(-n // 64) * b * H * n * 16
@@ -503,8 +475,8 @@ def test_attention_dropout_dh32_64_against_host_keep_bits(dh, p):
     qf, kf, vf = (t.to(DEV).requires_grad_() for t in (q, k, v))
     out = ops.attention(qf, kf, vf, lens.to(DEV), scale, p, seed=seed, offset=offset, sub=layer)
     (out * do.to(DEV)).sum().backward()
-    res = _attn_bwd_lib(q.to(DEV), k.to(DEV), v.to(DEV), lens.to(DEV), do.to(DEV), scale, p, False, seed=seed,
-                        offset=offset, sub=layer, nan_fill=True)
+    res = AH.attn_lib(q.to(DEV), k.to(DEV), v.to(DEV), lens.to(DEV), do.to(DEV), scale, p, 'two', 'plain', seed=seed,
+                      offset=offset, sub=layer)
     torch.cuda.synchronize()
     for name, t in list(res.items()) + [('out', out), ('qg', qf.grad), ('kg', kf.grad), ('vg', vf.grad)]:
         assert torch.isfinite(t).all(), name
@@ -547,10 +519,16 @@ def test_ff_dropout_mask_is_host_philox_stream(p, layer):
 def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, episodes=8, batch=4, seed=3,
                  hazard=3, mode='lander', dim=48, reward_dropout=0.5, gene_dim=8, agent_extra=None, fractal_levels=None,
                  ff_mult=4, genes=3, shard_by_gene=False, ff_no_bias=False, ff_glu=False, wm_extra=None, squash=True,
-                 heads=4, dim_head=16, device=None):
+                 heads=4, dim_head=16, device=None, window=None, window_key=True, kv_heads=None, num_mem_kv=0,
+                 add_zero_kv=False, use_graph=False, with_oracle=True):
     """``heads``, ``dim_head``: the attention geometry (world_model heads / attn_dim_head and the oracle's
     LearnerConfig fields).  ``device``: 'cpu' builds the Learner without a GPU (the same initial weights:
     test_geometry_cpu settles the cases' inputs from the oracle alone).
+    ``window``, ``num_mem_kv``, ``add_zero_kv``: world_model attn_max_attend_past (``window_key`` False: the key
+    is left out), attn_num_mem_kv and attn_add_zero_kv; ``kv_heads``: 1 goes in as world_model['attn_one_kv_head'],
+    any other count as agent_kwargs kv_heads, so both ways in are run.  These go to the Learner alone: the oracle
+    takes them from the Attention the caller has patched over the frozen one (attn_harness.rollout_and_learn).
+    ``with_oracle`` False: a device-only test, the third result is None.
     ``fractal_levels``: the causal fractal policy body (policy_body='fractal') on both sides.
     ``squash``: squash_continuous of the Learner / squash of the oracle (tanh-squashed continuous actions).
     ``ff_mult``: the feed-forward width through world_model['ff_mult'] (x-transformers' FeedForward mult).
@@ -572,7 +550,13 @@ def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, epi
         wm['ff_glu'] = True
     if gates:
         wm.update(attn_gate_values=True, add_value_residual=True, learned_value_residual_mix=True)
-    wm.update(wm_extra or {})
+    wm.update(wm_extra or {}, attn_num_mem_kv=num_mem_kv, attn_add_zero_kv=add_zero_kv)
+    if window_key:
+        wm['attn_max_attend_past'] = window
+    if kv_heads == 1:
+        wm['attn_one_kv_head'] = True
+    elif kv_heads is not None:
+        agent_extra = dict(agent_extra or {}, kv_heads=kv_heads)
     names = dict(attn_qk_norm='qk_norm', attn_qk_norm_scale='qk_norm_scale', rotary_xpos='rotary_xpos',
                  rotary_xpos_scale_base='xpos_scale_base', use_rmsnorm='rms_norm')
     oracle_extra = {names[k]: v for k, v in (wm_extra or {}).items()}
@@ -583,7 +567,7 @@ def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, epi
                       continuous_actions_clamp=(-1., 1.) if cont else None,
                       agent_kwargs=dict(dropout=0., seed=seed, hidden_dim=dim, reward_dropout=reward_dropout,
                                         **(agent_extra or {})),
-                      use_graph=False, shard_by_gene=shard_by_gene,
+                      use_graph=use_graph, shard_by_gene=shard_by_gene,
                       **(dict(accelerate_kwargs=dict(device=device)) if device is not None else {}))
     with torch.no_grad():   # non-trivial gate / mix weights (their init is constant)
         g = torch.Generator().manual_seed(seed + 1)
@@ -592,6 +576,8 @@ def make_learner(S=8, A=4, depth=2, gates=True, evo=False, cont=False, T=12, epi
                 p.copy_((torch.randn(p.shape, generator=g) * 0.3).to(p.device))
         learner.agent.ema_flat.copy_(learner.agent.flat.flat)
     env = SynthVecSim(S, A, mode, hazard_log2=hazard)
+    if not with_oracle:
+        return learner, env, None
     c = R.LearnerConfig(S, A, (-2., 2.), dim=dim, depth=depth, heads=heads, dim_head=dim_head, gate_values=gates,
                         value_residual=gates, learned_mix=gates, continuous=cont, squash=squash,
                         clamp=(-1., 1.) if cont else None, evolutionary=evo, evolve_every=1, evolve_after_step=0, gene_pool=gp, max_timesteps=T, batch_size=batch,
@@ -1329,17 +1315,24 @@ def test_deploy_forward_matches_oracle_cached_decode(frac, dim):
     """Agent.forward (online model, KV cache — and for the fractal body the level running sums —
     threaded through hiddens) vs the oracle module; dim 256: the one-launch feed-forward at E = 1."""
     learner, env, oracle = make_learner(depth=2, gates=frac is None, fractal_levels=frac, dim=dim)
+    deploy_parity(learner, oracle, 4)
+
+
+def deploy_parity(learner, oracle, steps, S=8):
+    """Agent.forward for ``steps`` steps (E = 1, the cache threaded through hiddens; non-trivial RSNorm
+    statistics, a reward on every second step) against the oracle module's cached decode: the actor's raw
+    outputs within 1e-4 + 1e-5.  Returns the last hiddens."""
     agent = learner.agent
-    agent.rs_mean.copy_(torch.linspace(-0.5, 0.5, 9))
-    agent.rs_var.copy_(torch.linspace(0.5, 2., 9))
-    rs = R.RSNormState(9)
+    agent.rs_mean.copy_(torch.linspace(-0.5, 0.5, S + 1))
+    agent.rs_var.copy_(torch.linspace(0.5, 2., S + 1))
+    rs = R.RSNormState(S + 1)
     rs.mean, rs.var = agent.rs_mean.cpu().clone(), agent.rs_var.cpu().clone()
     m = oracle.model
     m.eval()
     g = torch.Generator().manual_seed(2)
     hiddens, cache = None, None
-    for t in range(4):
-        s = torch.randn(8, generator=g)
+    for t in range(steps):
+        s = torch.randn(S, generator=g)
         reward = None if t % 2 == 0 else float(torch.randn((), generator=g))
         raw, hiddens = agent(s.numpy(), reward=reward, hiddens=hiddens)
         swr = rs.apply(torch.cat((s, torch.tensor([0. if reward is None else reward]))))
@@ -1347,6 +1340,7 @@ def test_deploy_forward_matches_oracle_cached_decode(frac, dim):
             r, _, _, _, cache = m(swr[:-1].reshape(1, 1, -1), rewards=None if reward is None else swr[-1],
                                   cache=cache)
         tol(raw, r.reshape(-1), 1e-4, 1e-5)
+    return hiddens
 
 
 class _Captured(Exception):
@@ -1394,11 +1388,16 @@ def test_ff_glu_fused_train_step_matches_autograd():
     _fused_vs_autograd(False, True, True, 0.25, 70, depth=2, episodes=16, batch=16, hazard=6, dim=128, ff_glu=True)
 
 
-def _fused_vs_autograd(cont, evo, gates, p, T, depth, episodes, batch, hazard, dim, fractal=None, ff_glu=False, **geom):
-    """``geom``: further make_learner keywords (S, A, heads, dim_head, ff_mult, squash: test_geometry_gpu)."""
-    learner, env, _ = make_learner(depth=depth, gates=gates, evo=evo, cont=cont, T=T, episodes=episodes,
-                                   batch=batch, seed=9, hazard=hazard, dim=dim, fractal_levels=fractal, ff_glu=ff_glu,
-                                   **geom)
+def _fused_vs_autograd(cont, evo, gates, p, T, depth, episodes, batch, hazard, dim, fractal=None, ff_glu=False,
+                       checks=None, **geom):
+    """``geom``: further make_learner keywords (S, A, heads, dim_head, ff_mult, squash: test_geometry_gpu; window,
+    kv_heads, num_mem_kv, add_zero_kv, with_oracle: the attention files); ``checks(learner, env, oracle)``: the
+    caller's own assertions on what was built."""
+    learner, env, oracle = make_learner(depth=depth, gates=gates, evo=evo, cont=cont, T=T, episodes=episodes,
+                                        batch=batch, seed=9, hazard=hazard, dim=dim, fractal_levels=fractal,
+                                        ff_glu=ff_glu, **geom)
+    if checks is not None:
+        checks(learner, env, oracle)
     agent = learner.agent
     agent.cfg.dropout = p
     agent.model.cfg.dropout = p
@@ -1665,8 +1664,9 @@ def test_packed_learn_matches_padded_step(evo, gates, T, dim, cont, wm):
 
 
 def _packed_vs_padded(evo, gates, T, dim, cont, wm, depth=2, **geom):
-    """The body of test_packed_learn_matches_padded_step; ``depth`` and ``geom`` (S, A, heads, dim_head, ...):
-    further make_learner keywords (test_geometry_gpu)."""
+    """The body of test_packed_learn_matches_padded_step; ``depth`` and ``geom`` (S, A, heads, dim_head, ...;
+    window, kv_heads, with_oracle): further make_learner keywords (test_geometry_gpu, the attention files).
+    Returns the packed step's first-minibatch state (its padded width ``n`` among it)."""
     res = {}
     glu = bool((wm or {}).get('ff_glu', False))
     extra = {k: v for k, v in (wm or {}).items() if k != 'ff_glu'} or None
@@ -1695,6 +1695,7 @@ def _packed_vs_padded(evo, gates, T, dim, cont, wm, depth=2, **geom):
         if float((g0 - g1).abs().max()) > 1e-4 * own + 1e-7:
             bad.append((name, float((g0 - g1).abs().max()), own))
     assert not bad, bad
+    return a
 
 
 @pytest.mark.parametrize('cfg', ['c3', 'c2'])
