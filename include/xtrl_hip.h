@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 25
+#define XTRL_ABI_VERSION 26
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -588,12 +588,15 @@ typedef struct XtrlTrainDesc {
   const float* d_values;
   const float* d_pred;
   const float* d_done;
-  /* backward scratch */
-  float* dx;                     /* [T][d] */
-  float* dx2;                    /* [T][d] second residual-gradient buffer (fused LayerNorm backward) */
+  /* backward scratch.  With the fused LayerNorms (d <= 256, every operand width a multiple of 4) the
+   * buffers the weight-gradient stream reads are per-layer planes, written once per backward, so the
+   * caller's stream never waits for that stream before the final join; otherwise one plane each,
+   * reused layer by layer behind events */
+  float* dx;                     /* fused [L + 1][T][d] (slot l + 1: w.r.t. block l's output), else [T][d] */
+  float* dx2;                    /* fused [L][T][d] (w.r.t. block l's attention output), else unused */
   float* dxn;                    /* [T][d] */
-  float* dff;                    /* [T][ff] */
-  float* dproj;                  /* [T][max n_qkv] */
+  float* dff;                    /* fused [L][T][ld] (ld = ld_ff, ff_glu: ld_u2), else [T][ld] */
+  float* dproj;                  /* fused [L][T][max n_qkv], else [T][max n_qkv] */
   float* dog;                    /* [T][I] */
   float* dvfirst;                /* [T][Ikv] */
   float* dz1;                    /* [T][4d] */
@@ -627,11 +630,6 @@ typedef struct XtrlTrainDesc {
    * >= ff, a multiple of 4; 0 = ff.  A stride off the 4 KiB power of two (e.g. ff + 16) spreads the
    * FF1 epilogue's two store streams over the memory channels */
   int ld_ff;
-  /* 1 (decoder step with the fused LayerNorms): the backward buffers the weight-gradient stream reads
-   * are per-layer planes — dx [L + 1][T][d], dx2 [L][T][d], dff [L][T][ld_ff], dproj [L][T][max n_qkv]
-   * — written once per backward, so the caller's stream never waits for the weight-gradient stream
-   * before the final join; 0: one plane each, reused layer by layer behind events */
-  int scratch_per_layer;
   /* world_model['ff_glu'] (x-transformers FeedForward glu = True): w_ff1 / b_ff1 are the GLU
    * projection [2 ff][d] / [2 ff] (value rows, then gate rows); per layer u holds its output
    * [T][ld_u2] (ld_u2 >= 2 ff, a multiple of 4) for the backward, dff is the projection's gradient

@@ -56,6 +56,9 @@ CASES = [
     Geometry('h8x16_max', 8, 16, 128, 32, 32, 1, True, ROWS_MULTI, 3, 4, 24, 12),
     Geometry('h16x16', 16, 16, 64, 8, 4, 2, True, ROWS_MULTI, 3, 4, 20, 8),
     Geometry('h4x32_d320', 4, 32, 320, 8, 6, 1, False, MULTI, 3, 4, 20, 8),
+    # two blocks past the fused LayerNorms (d > 256) and without the learned mix: the learn backward's
+    # single-plane scratch behind its cross-layer stream waits, every other operand a multiple of 4
+    Geometry('h4x32_d320_l2', 4, 32, 320, 8, 6, 2, False, MULTI, 3, 4, 20, 8),
     Geometry('h8x64_d512', 8, 64, 512, 8, 4, 1, False, MULTI, 3, 4, 16, 8, ff_mult=2),
     Geometry('cont_a1', 2, 32, 64, 5, 1, 2, True, ROWS_MULTI, 3, 4, 20, 8, cont=True),
     Geometry('cont_a6', 2, 64, 128, 5, 6, 2, True, ROWS_MULTI, 3, 4, 20, 8, cont=True, squash=False),

@@ -32,11 +32,13 @@ def test_fractal_oracle_rollout_meets_the_input_conditions():
 
 def test_case_table_holds_the_geometries_it_is_there_for():
     cs = GC.BY_ID
-    assert len(GC.CASES) == 9 and len(cs) == 9 + len(GC.EXTRA)
+    assert len(GC.CASES) == 10 and len(cs) == 10 + len(GC.EXTRA)
     assert {(c.H, c.dh) for c in GC.CASES} >= {(2, 32), (1, 64), (3, 16), (8, 16), (16, 16), (4, 32), (8, 64), (2, 64)}
     assert all(16 <= c.T <= 24 and 8 <= c.episodes <= 12 and c.episodes % c.batch == 0 for c in GC.CASES)
     # decode embedding: NC = 3 (d = 192), NC = 8 with d not a multiple of 512 (d = 320), d = 512
     assert {cs['h3x16_d192'].d, cs['h4x32_d320'].d, cs['h8x64_d512'].d} == {192, 320, 512}
+    # the learn backward without the fused LayerNorms (d > 256), more than one block deep
+    assert (cs['h4x32_d320_l2'].d, cs['h4x32_d320_l2'].depth) == (320, 2)
     # the learn step's limits (train.hip EMB_MAXS / EMB_MAXA) and the register-held action rows (EMB_AREG = 8)
     assert (cs['h8x16_max'].S, cs['h8x16_max'].A) == (32, 32) and cs['h3x16_d192'].A == 9 and cs['h1x64'].S == 1
     assert cs['h16x16'].H > 8                                   # the unfused out-projection at dh = 16

@@ -182,6 +182,42 @@ def test_packed_learn_matches_padded_step(cid):
     G._packed_vs_padded(c.evo, c.gates, 40, c.d, c.cont, None, depth=c.depth, **c.geom())
 
 
+@pytest.mark.parametrize('cid', ('h4x32_d320_l2', 'h2x32'))
+def test_bucketed_backward_equals_plain_backward(cid):
+    """xtrl_train_backward with data-parallel gradient buckets (grad_events: the deferred reductions flushed and
+    an event recorded on both streams per bucket) gives bitwise the gradient of the plain backward, on the
+    two-block backward without the fused LayerNorms (h4x32_d320_l2: d > 256; h2x32: the learned mix's n_qkv is
+    no multiple of 4) — the criterion of test_world1_rccl_bucket_allreduce_leaves_gradient_unchanged, without a
+    process group.  The backward is run again on the first minibatch's bound inputs (forward activations and
+    loss gradients, which it only reads); the control: two plain backwards agree bitwise."""
+    import ctypes as C
+    c = GC.BY_ID[cid]
+    learner, env, _ = G.make_learner(**c.learner_kwargs(), with_oracle=False)
+    agent = learner.agent
+    traj, lens, genes, cum = learner.rollout_device(env, 0, c.T)
+    assert agent.fused_learn
+    G._first_minibatch(agent, traj, lens, genes, learner.fitness(cum, genes))
+    step = agent.train_step(c.batch, c.T)   # (the step the minibatch ran on, its inputs still bound)
+
+    def backward(grad_events=None):
+        agent.flat.grad.zero_()
+        step.backward(grad_events=grad_events)
+        torch.cuda.synchronize()
+        return agent.flat.grad.clone()
+
+    plain = backward()
+    assert float(plain.abs().max()) > 0
+    assert torch.equal(backward(), plain)
+    # 2 (depth + 2) events, created and recorded once (as distributed.BucketAllReduce.__init__)
+    events = [torch.cuda.Event() for _ in range(2 * (c.depth + 2))]
+    for e in events:
+        e.record()
+    handles = (C.c_void_p * len(events))(*[e.cuda_event for e in events])
+    bucketed = backward(handles)
+    assert all(e.query() for e in events)
+    assert torch.equal(bucketed, plain)
+
+
 @pytest.mark.parametrize('cid', GC.DEPLOY)
 def test_deploy_forward_matches_oracle_cached_decode(cid):
     """Agent.forward for 6 steps (E = 1, the KV cache threaded through hiddens) against the oracle's cached

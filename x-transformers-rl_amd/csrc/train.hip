@@ -1049,6 +1049,106 @@ int colsum(const Ctx& c, const float* src, int ld, int rows, int cols, float* ds
   return XTRL_OK;
 }
 
+// ---- what the backward of every policy body (decoder, fractal) runs on -------------------------
+// The two streams of one backward call: the main-stream context c; the weight-gradient context cw
+// (the side stream, split-K partials summed by one launch per flush); the fused decoder path's
+// deferred LayerNorm column sums (csq: empty otherwise, its flush a no-op); the data-parallel
+// gradient buckets.  what ("train" / "fractal train") prefixes the error texts.
+struct Backward {
+  const XtrlTrainDesc* D;
+  const char* what;
+  size_t events_needed;
+  Fork F;
+  SplitKQueue skq;
+  ColsumQueue csq;
+  Ctx c, cw;
+  int bucket = 0;
+  bool wpin_on_main = false;
+  // (main: the caller's stream and row count)
+  Backward(const Ctx& main, size_t events, const char* what_)
+      : D(main.D), what(what_), events_needed(events), F{main.s, nullptr, nullptr}, c(main), cw(main) {
+    SideStream& side = side_stream();
+    if (side.ok && side.ensure(events)) {
+      F.side = side.s;
+      F.S = &side;
+      cw.s = side.s;
+    }
+    cw.q = &skq;
+  }
+  Backward(const Backward&) = delete;   // (cw points into this object)
+  // a gradient bucket is final: flush its deferred reductions, then record its event on both streams
+  int bucket_done() {
+    if (!D->grad_events) return XTRL_OK;
+    if (int rc = csq.flush(c.s)) return rc;
+    if (int rc = splitk_flush(skq, cw.s)) return rc;
+    if (hipEventRecord((hipEvent_t)D->grad_events[2 * bucket], c.s) != hipSuccess ||
+        hipEventRecord((hipEvent_t)D->grad_events[2 * bucket + 1], cw.s) != hipSuccess) {
+      set_error("%s: gradient bucket event record failed", what);
+      return XTRL_E_HIP;
+    }
+    ++bucket;
+    return XTRL_OK;
+  }
+  // discrete action-embedding gradient (k_embed_grad_part's operands; no prev: nullptr, 0, nullptr)
+  // into dst [A][d]: 16-row partials (loads in flight), as many as the partial workspace holds
+  int embed_grad(const float* g1, int ld1, const int32_t* prev, const float* g2, int ld2, const int32_t* next,
+                 float* dst) {
+    const int T = c.T, d = D->d, A = D->A;
+    const hipStream_t s = c.s;
+    int chunks = (int)std::min<int64_t>(std::min(1024, std::max(1, T / 16)),
+                                        std::max<int64_t>(1, D->part_floats / ((int64_t)A * d)));
+    const int chunk_rows = (T + chunks - 1) / chunks;
+    chunks = (T + chunk_rows - 1) / chunk_rows;
+    XTRL_REQUIRE((int64_t)chunks * A * d <= D->part_floats, "%s: partial-sum workspace too small", what);
+    const dim3 eg(blocks(d, 256), chunks);
+    if (A <= 4)
+      hipLaunchKernelGGL(k_embed_grad_part<4>, eg, dim3(256), 0, s, g1, ld1, prev, g2, ld2, next, T, d, A, chunk_rows,
+                         D->part);
+    else if (A <= 8)
+      hipLaunchKernelGGL(k_embed_grad_part<8>, eg, dim3(256), 0, s, g1, ld1, prev, g2, ld2, next, T, d, A, chunk_rows,
+                         D->part);
+    else
+      hipLaunchKernelGGL(k_embed_grad_part<EMB_MAXA>, eg, dim3(256), 0, s, g1, ld1, prev, g2, ld2, next, T, d, A,
+                         chunk_rows, D->part);
+    hipLaunchKernelGGL(k_colsum_final, dim3(blocks(A * d, CS_COLS)), dim3(64 * CS_WAVES), 0, s, D->part, chunks, A * d,
+                       dst);
+    if (const hipError_t e = hipGetLastError()) {
+      set_error("%s embed grad: %s", what, hipGetErrorString(e));
+      return XTRL_E_HIP;
+    }
+    return XTRL_OK;
+  }
+  // the input projection's weight gradient from dY [T][d] (+ its bias gradient db), last of the
+  // backward.  The queued split-K sums start now on the side stream, beside the embedding backward,
+  // and this small gradient runs on the main stream into the workspace behind them (its immediate
+  // reduce; the backward's tail was that gradient waiting for its fork, then the whole flush).
+  // Otherwise (!main_ok, gradient buckets, a full workspace): on the side stream, before the flush.
+  int input_proj_wgrad(const float* dY, float* db, bool main_ok) {
+    const int d = D->d, S = D->S;
+    wpin_on_main = main_ok && !D->grad_events && skq.used < D->ws_floats;
+    if (wpin_on_main) {
+      const int64_t used0 = skq.used;
+      if (int rc = splitk_flush(skq, cw.s)) return rc;
+      return gemm_wgrad(dY, d, D->swr, S + 1, c.G(D->w_pin), S, c.T, d, S, 1.f, D->ws + used0, D->ws_floats - used0,
+                        c.s, db, 0, nullptr, nullptr);
+    }
+    if (int rc = F.fork()) return rc;
+    return wgrad(cw, dY, d, D->swr, S + 1, c.G(D->w_pin), c.T, d, S, db);
+  }
+  // every weight gradient is in before the caller's optimiser step: the last flush and bucket (the
+  // embeddings, and the flat buffer's tail), the join, and the count of the events taken
+  int finish() {
+    int rc;
+    if ((rc = splitk_flush(skq, cw.s))) return rc;
+    if ((rc = bucket_done())) return rc;
+    if ((rc = F.wait(F.mark()))) return rc;
+    XTRL_REQUIRE(!F.failed, "%s: side-stream event record failed", what);
+    const int need = (int)events_needed - (wpin_on_main ? 1 : 0);   // (on the main stream: no fork)
+    XTRL_REQUIRE(!F.on() || F.next == need, "%s: side events %d != %d", what, F.next, need);
+    return XTRL_OK;
+  }
+};
+
 int ln_fwd(const Ctx& c, const float* x, const float* gamma, float* y1, int ld1, float* y2, int ld2, float* st) {
   hipLaunchKernelGGL(k_ln_fwd, dim3(blocks(c.T, 4)), dim3(256), 0, c.s, x, gamma, y1, ld1, y2, ld2, st, c.T,
                      c.D->d, c.D->rms_norm);
@@ -1495,47 +1595,38 @@ int train_forward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
 int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
   if (int rc = validate(D)) return rc;
   XTRL_REQUIRE(D->d_raw && D->d_values && D->d_pred && D->d_done, "train: missing loss gradients");
-  const Ctx c{D, s, Trows};
+  // weight gradients on the side stream; their split-K partials are summed by one launch at the end
+  Backward B(Ctx{D, s, Trows}, side_events_needed(D->L), "train");
+  const Ctx &c = B.c, &cw = B.cw;
+  Fork& F = B.F;
+  ColsumQueue& csq = B.csq;
   const int32_t* rows = D->packed ? D->vrows : nullptr;
   const int T = c.T, d = D->d, I = D->H * D->dh, ff = D->ff, lf = ld_ff(D);
   const int Ikv = kv_inner(D), nq3 = I + 2 * Ikv;   // the k / v segment width; q | k | v columns of a projection row
   int rc;
-  SideStream& side = side_stream();
-  const bool two = side.ok && side.ensure(side_events_needed(D->L));
-  Fork F{s, side.s, two ? &side : nullptr};
-  // the LayerNorm d gamma sums of the final norm and the decoder blocks: deferred to one launch after
-  // the blocks (nothing else writes the partial workspace until the embeddings), or at each gradient
-  // bucket
-  ColsumQueue csq;
-  if (ln_fusable(D) && D->scratch_per_layer) {
+  // The two modes of this backward.  Fused (ln_fusable): every LayerNorm backward runs in a GEMM
+  // epilogue, and every buffer a side-stream weight gradient reads is a per-layer plane written once
+  // per backward — dx [L + 1][T][d] (slot l + 1: the gradient w.r.t. block l's output, slot 0 w.r.t.
+  // the embedding), dx2 [L][T][d] (w.r.t. block l's attention output), dff [L][T][ld_f1], dproj
+  // [L][T][max n_qkv] — so the main stream never waits for the side stream before the final join.
+  // Unfused (d > 256 or an operand not a multiple of 4): one plane each, reused layer by layer
+  // behind four waits per block.
+  const bool fuse = ln_fusable(D);
+  XTRL_REQUIRE(!fuse || D->dx2, "train: fused LayerNorm backward needs dx2");
+  // (fused) the LayerNorm d gamma sums of the final norm and the decoder blocks: deferred to one launch
+  // after the blocks (nothing else writes the partial workspace until the embeddings), or at each
+  // gradient bucket
+  if (fuse) {
     csq.base = D->part;
     csq.cap = D->part_floats;
   }
-  // weight gradients (side stream); their split-K partials are summed by one launch at the end
-  SplitKQueue skq;
-  const Ctx cw{D, two ? side.s : s, T, &skq};
-  // data-parallel gradient buckets: flush the bucket's deferred reductions, then record its events
-  int bucket = 0;
-  auto bucket_done = [&]() -> int {
-    if (!D->grad_events) return XTRL_OK;
-    if (int rc = csq.flush(s)) return rc;
-    if (int rc = splitk_flush(skq, cw.s)) return rc;
-    if (hipEventRecord((hipEvent_t)D->grad_events[2 * bucket], s) != hipSuccess ||
-        hipEventRecord((hipEvent_t)D->grad_events[2 * bucket + 1], cw.s) != hipSuccess) {
-      set_error("train: gradient bucket event record failed");
-      return XTRL_E_HIP;
-    }
-    ++bucket;
-    return XTRL_OK;
-  };
-  const bool per_layer = ln_fusable(D) && D->scratch_per_layer;
-  float* dx_top = per_layer ? D->dx + (int64_t)D->L * T * d : D->dx;   // (scratch_per_layer: slot L)
+  const int64_t Td = (int64_t)T * d;
+  float* dx_top = fuse ? D->dx + D->L * Td : D->dx;
   // ---- final norm: d embed = frac * dac[:, :d] + dewa[:, :d].  Fused: the embed columns of the
   // actor | critic input gradient finish the final norm's backward in their GEMM's epilogue (no
   // LayerNorm launch); otherwise dac in full, then k_ln_bwd
-  const bool fold = ln_fusable(D);
-  if ((rc = heads_backward(c, cw, F, !fold))) return rc;
-  if (fold) {
+  if ((rc = heads_backward(c, cw, F, !fuse))) return rc;
+  if (fuse) {
     const int nb = (T + gemm_ln_rows(d) - 1) / gemm_ln_rows(d);
     XTRL_REQUIRE((int64_t)nb * d <= D->part_floats, "train: partial-sum workspace too small");
     GemmArgs g;
@@ -1555,34 +1646,28 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
                           c.P(D->ln_final), nullptr, dx_top, c.G(D->ln_final)))) {
     return rc;
   }
-  if ((rc = bucket_done())) return rc;   // bucket 0: heads, state / gene embeddings, final norm
-  // ---- decoder blocks, last to first.  Side events of the weight gradients whose dY buffer the
-  // main stream overwrites later: dx (FF2 / out-projection), dff (FF1, by the next layer's FF2
-  // input gradient), dproj (q|k|v projection, by the next layer's gate / attention backward).
-  // Fused LayerNorm backward (ln_fusable): the FF1 and q|k|v input-gradient GEMMs finish the
-  // LayerNorm backward and add the residual gradient in their epilogue, alternating between dx and
-  // dx2, so neither overwrites the buffer a pending side-stream weight gradient still reads: the FF
-  // block writes dx2 (read by the out-projection weight gradient), the attention block writes dx
-  // (read by the next FF2 weight gradient).
-  const bool fuse = ln_fusable(D);
-  XTRL_REQUIRE(!fuse || D->dx2, "train: fused LayerNorm backward needs dx2");
-  // scratch_per_layer (fused path): every buffer a side-stream weight gradient reads is a per-layer
-  // plane written once per backward — dx [L + 1][T][d] (slot l + 1: the gradient w.r.t. block l's
-  // output, slot 0 w.r.t. the embedding), dx2 [L][T][d] (w.r.t. block l's attention output), dff
-  // [L][T][ld_ff], dproj [L][T][max n_qkv] — so the main stream never waits for the side stream
-  // before the final join (the waits below are skipped)
-  const bool per = per_layer;
+  if ((rc = B.bucket_done())) return rc;   // bucket 0: heads, state / gene embeddings, final norm
+  // ---- decoder blocks, last to first.  Unfused: the main stream waits for the side events of the
+  // weight gradients whose dY buffer it is about to overwrite: dff (FF1, by the next layer's FF2
+  // input gradient), dx (FF2 / out-projection, by the LayerNorm backward), dproj (q|k|v projection, by
+  // the next layer's gate / attention backward).  Fused: the FF1 and q|k|v input-gradient GEMMs finish
+  // the LayerNorm backward and add the residual gradient in their epilogue; the FF block writes dx2
+  // (read by the out-projection weight gradient), the attention block writes dx (read by the next FF2
+  // weight gradient), each into its layer's plane.
   int maxq = 0;
   for (int li = 0; li < D->L; ++li) maxq = std::max(maxq, D->layers[li].n_qkv);
-  const int64_t Td = (int64_t)T * d;
-  auto Gx = [&](int slot) { return per ? D->dx + slot * Td : D->dx; };
-  auto Gx2 = [&](int li) { return per ? D->dx2 + li * Td : D->dx2; };
+  auto Gx = [&](int slot) { return fuse ? D->dx + slot * Td : D->dx; };
+  auto Gx2 = [&](int li) { return fuse ? D->dx2 + li * Td : D->dx2; };
   // dff: the FF1 output gradient [T][ld_f1] (GLU: the projection's [T][2 ff] on the ld_u2 stride)
   const int f1 = D->ff_glu ? 2 * ff : ff, ld_f1 = D->ff_glu ? D->ld_u2 : lf;
-  auto Gff = [&](int li) { return per ? D->dff + (int64_t)li * T * ld_f1 : D->dff; };
-  auto Gpr = [&](int li) { return per ? D->dproj + (int64_t)li * T * maxq : D->dproj; };
-  auto wait = [&](hipEvent_t e) { return per ? XTRL_OK : F.wait(e); };
-  hipEvent_t e_ff1 = nullptr, e_proj = nullptr, e_out_prev = nullptr;
+  auto Gff = [&](int li) { return fuse ? D->dff + (int64_t)li * T * ld_f1 : D->dff; };
+  auto Gpr = [&](int li) { return fuse ? D->dproj + (int64_t)li * T * maxq : D->dproj; };
+  const bool any_mix = [&] {
+    for (int j = 1; j < D->L; ++j)
+      if (D->layers[j].mix) return true;
+    return false;
+  }();
+  hipEvent_t e_ff1 = nullptr, e_proj = nullptr;   // (unfused) the deeper block's FF1 / projection weight gradients
   for (int li = D->L - 1; li >= 0; --li) {
     const XtrlTrainLayer& Ly = D->layers[li];
     float* gout = Gx(li + 1);   // gradient w.r.t. the block output
@@ -1592,7 +1677,7 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     if ((rc = F.fork())) return rc;
     if ((rc = wgrad(cw, gout, d, Ly.hd, lf, c.G(Ly.w_ff2), T, d, ff, c.G(Ly.b_ff2)))) return rc;
     hipEvent_t e_ff2 = F.mark();
-    if ((rc = wait(e_ff1))) return rc;
+    if (!fuse && (rc = F.wait(e_ff1))) return rc;   // the deeper block's FF1 weight gradient read dff
     if (D->ff_glu) {   // d hd, then the GLU backward into the projection gradient
       if ((rc = linear_dgrad(c, gout, d, c.P(Ly.w_ff2), D->glu_dh, lf, T, d, ff, EPI_NONE))) return rc;
       if ((rc = glu_bwd(D->glu_dh, lf, Ly.u, D->ld_u2, dff, ld_f1, T, ff, D->dropout, D->seed, D->ff_offset,
@@ -1606,14 +1691,13 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     e_ff1 = F.mark();
     float* xg = D->dx;   // gradient w.r.t. the attention block's output
     if (fuse) {
-      if ((rc = wait(e_out_prev))) return rc;   // the deeper block's out-projection weight gradient read dx2
       if ((rc = dgrad_ln_bwd(c, dff, ld_f1, c.P(Ly.w_ff1), f1, Ly.x_ff, Ly.st_ff, c.P(Ly.ln_ff), gout, Gx2(li),
                              c.G(Ly.ln_ff), &csq)))
         return rc;
       xg = Gx2(li);
     } else {
       if ((rc = linear_dgrad(c, dff, ld_f1, c.P(Ly.w_ff1), D->dxn, d, T, f1, d, EPI_NONE))) return rc;
-      if ((rc = F.wait(e_ff2))) return rc;
+      if ((rc = F.wait(e_ff2))) return rc;   // this block's FF2 weight gradient read dx
       if ((rc = ln_bwd(c, D->dxn, d, 1.f, nullptr, 0, Ly.x_ff, Ly.st_ff, c.P(Ly.ln_ff), D->dx, D->dx, c.G(Ly.ln_ff))))
         return rc;
     }
@@ -1621,7 +1705,7 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     if ((rc = F.fork())) return rc;
     if ((rc = wgrad(cw, xg, d, D->gate_values ? Ly.og : Ly.o, I, c.G(Ly.w_out), T, d, I))) return rc;
     hipEvent_t e_out = F.mark();
-    if ((rc = wait(e_proj))) return rc;
+    if (!fuse && (rc = F.wait(e_proj))) return rc;   // the deeper block's projection weight gradient read dproj
     if (D->gate_values) {
       if ((rc = linear_dgrad(c, xg, d, c.P(Ly.w_out), D->dog, I, T, d, I, EPI_DGATE, Ly.o, I, 1 << 30,
                              Ly.proj + nq3, Ly.n_qkv, dproj + nq3, Ly.n_qkv)))
@@ -1634,11 +1718,6 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
                           dproj + I + Ikv, D->delta, s)))
       return rc;
     const int mix_col = Ly.mix ? nq3 + (D->gate_values ? I : 0) : -1;
-    const bool any_mix = [&] {
-      for (int j = 1; j < D->L; ++j)
-        if (D->layers[j].mix) return true;
-      return false;
-    }();
     // dvfirst: the first mixing layer processed (the deepest) writes, the others accumulate
     bool deeper_mix = false;
     for (int j = li + 1; j < D->L; ++j) deeper_mix = deeper_mix || D->layers[j].mix;
@@ -1654,71 +1733,32 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
       return rc;
     e_proj = F.mark();
     if (fuse) {
-      if ((rc = wait(e_ff2))) return rc;   // this block's FF2 weight gradient read dx
       if ((rc = dgrad_ln_bwd(c, dproj, Ly.n_qkv, c.P(Ly.w_proj), Ly.n_qkv, Ly.x_attn, Ly.st_attn, c.P(Ly.ln_attn),
                              Gx2(li), Gx(li), c.G(Ly.ln_attn), &csq)))
         return rc;
-      e_out_prev = e_out;
     } else {
       if ((rc = linear_dgrad(c, dproj, Ly.n_qkv, c.P(Ly.w_proj), D->dxn, d, T, Ly.n_qkv, d, EPI_NONE))) return rc;
-      if ((rc = F.wait(e_out))) return rc;
+      if ((rc = F.wait(e_out))) return rc;   // this block's out-projection weight gradient read dx
       if ((rc = ln_bwd(c, D->dxn, d, 1.f, nullptr, 0, Ly.x_attn, Ly.st_attn, c.P(Ly.ln_attn), D->dx, D->dx,
                        c.G(Ly.ln_attn))))
         return rc;
     }
-    if ((rc = bucket_done())) return rc;   // bucket L - li: decoder block li
+    if ((rc = B.bucket_done())) return rc;   // bucket L - li: decoder block li
   }
   if ((rc = csq.flush(s))) return rc;   // (before the embeddings reuse the partial workspace)
-  // ---- embeddings: dx is d x0.  The deferred split-K sums start now on the side stream, beside the
-  // embedding backward, and project_in's small weight gradient runs on the main stream into the
-  // workspace behind them (its immediate reduce; the backward's tail was that gradient waiting for its
-  // fork, then the whole flush).  Otherwise: on the side stream, before the flush.
-  const bool wpin_on_main = !D->continuous && !D->grad_events && skq.used < D->ws_floats;
-  if (wpin_on_main) {
-    const int64_t used0 = skq.used;
-    if ((rc = splitk_flush(skq, cw.s))) return rc;
-    if ((rc = gemm_wgrad(D->dx, d, D->swr, D->S + 1, c.G(D->w_pin), D->S, T, d, D->S, 1.f, D->ws + used0,
-                         D->ws_floats - used0, s, nullptr, 0, nullptr, nullptr)))
-      return rc;
-  } else {
-    if ((rc = F.fork())) return rc;
-    if ((rc = wgrad(cw, D->dx, d, D->swr, D->S + 1, c.G(D->w_pin), T, d, D->S))) return rc;
-  }
+  // ---- embeddings: dx is d x0.  project_in's weight gradient (continuous actions: on the side
+  // stream, with the action embedding's below)
+  if ((rc = B.input_proj_wgrad(D->dx, nullptr, !D->continuous))) return rc;
   if ((rc = colsum(c, D->dx, d, T, d, c.G(D->reward_embed), D->swr + D->S, D->S + 1, D->reward_keep))) return rc;
   if (D->continuous) {
     if ((rc = wgrad(cw, D->dx, d, D->prev_action_f, D->A, c.G(D->act_emb), T, d, D->A))) return rc;
     if ((rc = wgrad(cw, D->dewa + d, 2 * d, D->next_action_f, D->A, c.G(D->act_emb), T, d, D->A))) return rc;
     if ((rc = colsum(c, D->dx, d, T, d, c.G(D->act_emb_b)))) return rc;
     if ((rc = colsum(c, D->dewa + d, 2 * d, T, d, c.G(D->act_emb_b)))) return rc;
-  } else {
-    // 16-row partials (loads in flight), as many as the partial workspace holds
-    int chunks = std::min<int64_t>(std::min(1024, std::max(1, T / 16)),
-                                   std::max<int64_t>(1, D->part_floats / ((int64_t)D->A * d)));
-    const int chunk_rows = (T + chunks - 1) / chunks;
-    chunks = (T + chunk_rows - 1) / chunk_rows;
-    XTRL_REQUIRE((int64_t)chunks * D->A * d <= D->part_floats, "train: partial-sum workspace too small");
-    const dim3 eg(blocks(d, 256), chunks);
-    if (D->A <= 4)
-      hipLaunchKernelGGL(k_embed_grad_part<4>, eg, dim3(256), 0, s, D->dx, d, D->prev_action, D->dewa + d, 2 * d,
-                         D->next_action, T, d, D->A, chunk_rows, D->part);
-    else if (D->A <= 8)
-      hipLaunchKernelGGL(k_embed_grad_part<8>, eg, dim3(256), 0, s, D->dx, d, D->prev_action, D->dewa + d, 2 * d,
-                         D->next_action, T, d, D->A, chunk_rows, D->part);
-    else
-      hipLaunchKernelGGL(k_embed_grad_part<EMB_MAXA>, eg, dim3(256), 0, s, D->dx, d, D->prev_action, D->dewa + d,
-                         2 * d, D->next_action, T, d, D->A, chunk_rows, D->part);
-    hipLaunchKernelGGL(k_colsum_final, dim3(blocks(D->A * d, CS_COLS)), dim3(64 * CS_WAVES), 0, s, D->part, chunks, D->A * d,
-                       c.G(D->act_emb));
-    XTRL_LAUNCHED("train embed grad");
+  } else if ((rc = B.embed_grad(D->dx, d, D->prev_action, D->dewa + d, 2 * d, D->next_action, c.G(D->act_emb)))) {
+    return rc;
   }
-  // every weight gradient is in before the caller's optimiser step
-  if ((rc = splitk_flush(skq, cw.s))) return rc;
-  if ((rc = bucket_done())) return rc;   // bucket L + 1: embeddings (and the flat buffer's tail)
-  if ((rc = F.wait(F.mark()))) return rc;
-  XTRL_REQUIRE(!F.failed, "train: side-stream event record failed");
-  XTRL_REQUIRE(!F.on() || (size_t)F.next == side_events_needed(D->L) - (wpin_on_main ? 1 : 0),
-               "train: side events %d != %d", F.next, (int)side_events_needed(D->L) - (wpin_on_main ? 1 : 0));
-  return XTRL_OK;
+  return B.finish();
 }
 
 // ============================================================================================
@@ -2019,31 +2059,15 @@ int fractal_train_backward(const XtrlTrainDesc* D, const XtrlFractalTrainDesc* F
   XTRL_REQUIRE(F->dxa && F->dxb && F->ds && F->dmean && F->dga && F->dgv && F->dz && F->dqkv && F->dob && F->dcat &&
                    F->dhfa,
                "fractal train: missing backward scratch");
-  const Ctx c{D, s, D->b * D->n};
-  const int T = c.T, d = D->d, I = D->H * D->dh, ff = D->ff, lf = ld_ff(D), Lv = F->levels, S = D->S,
-            ldcat = (Lv + 1) * d;
+  const int Lv = F->levels;
+  // data-parallel gradient buckets (FractalPolicyActorCritic.flat_buckets_names): [heads, action
+  // embedding, final aggregation], one per level (last to first), [the rest]
+  Backward B(Ctx{D, s, D->b * D->n}, fractal_events_needed(Lv), "fractal train");
+  const Ctx &c = B.c, &cw = B.cw;
+  Fork& Fk = B.F;
+  const int T = c.T, d = D->d, I = D->H * D->dh, ff = D->ff, lf = ld_ff(D), ldcat = (Lv + 1) * d;
   const int64_t Td = (int64_t)T * d;
   int rc;
-  SideStream& side = side_stream();
-  const bool two = side.ok && side.ensure(fractal_events_needed(Lv));
-  Fork Fk{s, side.s, two ? &side : nullptr};
-  SplitKQueue skq;
-  const Ctx cw{D, two ? side.s : s, T, &skq};
-  // data-parallel gradient buckets (FractalPolicyActorCritic.flat_buckets_names): [heads, action
-  // embedding, final aggregation], one per level (last to first), [the rest]; each flushes its
-  // deferred split-K reductions and records an event on both streams once its gradients are final
-  int bucket = 0;
-  auto bucket_done = [&]() -> int {
-    if (!D->grad_events) return XTRL_OK;
-    if (int rc = splitk_flush(skq, cw.s)) return rc;
-    if (hipEventRecord((hipEvent_t)D->grad_events[2 * bucket], s) != hipSuccess ||
-        hipEventRecord((hipEvent_t)D->grad_events[2 * bucket + 1], cw.s) != hipSuccess) {
-      set_error("fractal train: gradient bucket event record failed");
-      return XTRL_E_HIP;
-    }
-    ++bucket;
-    return XTRL_OK;
-  };
   if ((rc = heads_backward(c, cw, Fk))) return rc;
   // d features = frac * dac[:, :d] + dewa[:, :d]  (frac_gradient: the actor / critic share scaled)
   // every backward scratch plane a side-stream weight gradient reads is written once per backward
@@ -2056,24 +2080,7 @@ int fractal_train_backward(const XtrlTrainDesc* D, const XtrlFractalTrainDesc* F
     if ((rc = wgrad(cw, D->dewa + d, 2 * d, D->next_action_f, D->A, c.G(D->act_emb), T, d, D->A, c.G(D->act_emb_b))))
       return rc;
   } else {
-    int chunks = (int)std::min<int64_t>(std::min(1024, std::max(1, T / 16)),
-                                        std::max<int64_t>(1, D->part_floats / ((int64_t)D->A * d)));
-    const int chunk_rows = (T + chunks - 1) / chunks;
-    chunks = (T + chunk_rows - 1) / chunk_rows;
-    XTRL_REQUIRE((int64_t)chunks * D->A * d <= D->part_floats, "fractal train: partial-sum workspace too small");
-    const dim3 eg(blocks(d, 256), chunks);
-    if (D->A <= 4)
-      hipLaunchKernelGGL(k_embed_grad_part<4>, eg, dim3(256), 0, s, nullptr, 0, nullptr, D->dewa + d, 2 * d,
-                         D->next_action, T, d, D->A, chunk_rows, D->part);
-    else if (D->A <= 8)
-      hipLaunchKernelGGL(k_embed_grad_part<8>, eg, dim3(256), 0, s, nullptr, 0, nullptr, D->dewa + d, 2 * d,
-                         D->next_action, T, d, D->A, chunk_rows, D->part);
-    else
-      hipLaunchKernelGGL(k_embed_grad_part<EMB_MAXA>, eg, dim3(256), 0, s, nullptr, 0, nullptr, D->dewa + d, 2 * d,
-                         D->next_action, T, d, D->A, chunk_rows, D->part);
-    hipLaunchKernelGGL(k_colsum_final, dim3(blocks(D->A * d, CS_COLS)), dim3(64 * CS_WAVES), 0, s, D->part, chunks,
-                       D->A * d, c.G(D->act_emb));
-    XTRL_LAUNCHED("fractal action embed grad");
+    if ((rc = B.embed_grad(nullptr, 0, nullptr, D->dewa + d, 2 * d, D->next_action, c.G(D->act_emb)))) return rc;
     if ((rc = Fk.fork())) return rc;   // (keeps the event count independent of the action kind)
   }
   // final aggregation: feat = hfa W_fa2^T + b; hfa = ReLU(cat W_fa0^T + b)
@@ -2082,7 +2089,7 @@ int fractal_train_backward(const XtrlTrainDesc* D, const XtrlFractalTrainDesc* F
   if ((rc = Fk.fork())) return rc;
   if ((rc = wgrad(cw, F->dhfa, 2 * d, F->cat, ldcat, c.G(F->w_fa0), T, 2 * d, ldcat, c.G(F->b_fa0)))) return rc;
   if ((rc = linear_dgrad(c, F->dhfa, 2 * d, c.P(F->w_fa0), F->dcat, ldcat, T, 2 * d, ldcat, EPI_NONE))) return rc;
-  if ((rc = bucket_done())) return rc;   // bucket 0: heads, action embedding, final aggregation
+  if ((rc = B.bucket_done())) return rc;   // bucket 0: heads, action embedding, final aggregation
   // levels, last to first.  dgn: gradient of g_{l+1} (the final g: cat's last d columns); dxn:
   // gradient of x3_l from level l + 1's input (none for the last level).
   // the chained post-norm LayerNorm backward epilogue (d > 256 or ff % 4: separate launches)
@@ -2154,30 +2161,12 @@ int fractal_train_backward(const XtrlTrainDesc* D, const XtrlFractalTrainDesc* F
     dxn = F->dxa;
     dgn = dgc;
     lddgn = d;
-    if ((rc = bucket_done())) return rc;   // bucket Lv - l: level l's block and projection
+    if ((rc = B.bucket_done())) return rc;   // bucket Lv - l: level l's block and projection
   }
-  // input embedding (x_in,0 = state W_in^T + b_in + le[0]) and global_state_init (g_0 on every row).
-  // As the decoder step's backward: the queued split-K sums start on the side stream here and the
-  // small input-projection gradient runs on the main stream behind them in the workspace
-  const bool wpin_on_main = !D->grad_events && skq.used < D->ws_floats;
-  if (wpin_on_main) {
-    const int64_t used0 = skq.used;
-    if ((rc = splitk_flush(skq, cw.s))) return rc;
-    if ((rc = gemm_wgrad(F->dxa, d, D->swr, S + 1, c.G(D->w_pin), S, T, d, S, 1.f, D->ws + used0,
-                         D->ws_floats - used0, c.s, c.G(F->b_in), 0, nullptr, nullptr)))
-      return rc;
-  } else {
-    if ((rc = Fk.fork())) return rc;
-    if ((rc = wgrad(cw, F->dxa, d, D->swr, S + 1, c.G(D->w_pin), T, d, S, c.G(F->b_in)))) return rc;
-  }
+  // input embedding (x_in,0 = state W_in^T + b_in + le[0]) and global_state_init (g_0 on every row)
+  if ((rc = B.input_proj_wgrad(F->dxa, c.G(F->b_in), true))) return rc;
   if ((rc = colsum(c, dgn, lddgn, T, d, c.G(F->g_init)))) return rc;
-  if ((rc = splitk_flush(skq, cw.s))) return rc;
-  if ((rc = bucket_done())) return rc;   // bucket Lv + 1: embeddings, global state, level embeddings
-  if ((rc = Fk.wait(Fk.mark()))) return rc;
-  XTRL_REQUIRE(!Fk.failed, "fractal train: side-stream event record failed");
-  XTRL_REQUIRE(!Fk.on() || (size_t)Fk.next == fractal_events_needed(Lv) - (wpin_on_main ? 1 : 0),
-               "fractal train: side events %d != %d", Fk.next, (int)fractal_events_needed(Lv) - (wpin_on_main ? 1 : 0));
-  return XTRL_OK;
+  return B.finish();   // bucket Lv + 1: embeddings, global state, level embeddings
 }
 
 }  // namespace xtrl

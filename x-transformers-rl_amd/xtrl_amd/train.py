@@ -203,7 +203,6 @@ class FusedTrainStep:
         D.ws, D.ws_floats = ws.data_ptr(), ws.numel()
         D.layers = C.cast(layers, C.POINTER(L.TrainLayer))
         D.ld_ff = lff
-        D.scratch_per_layer = 1   # per-layer backward planes (no mid-backward stream waits)
         D.ff_glu, D.ld_u2 = int(glu), (lu2 if glu else 0)
         self.cbuf = _compact_bufs(D, c, T, dev, b_max, n_max)
         self.D = D
