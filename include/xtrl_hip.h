@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 26
+#define XTRL_ABI_VERSION 27
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -248,6 +248,13 @@ typedef struct XtrlDecodeDesc {
    * [E][Ikv]: the resident cache and the cache read shrink by H / Hkv.  0: Hkv = H (a zero-initialised
    * descriptor is plain multi-head attention) */
   int Hkv;
+  /* ALiBi (ABI 27): world_model['alibi_pos_bias'] (x-transformers AlibiPositionalBias).  Device float [H],
+   * one slope per query head (0: that head takes no bias; the caller owns the length).  The step-t query's
+   * score against the cached key at position j is scale q . k_j - alibi_slopes[h] (t - j); the new key
+   * (j = t) and the sinks take no bias.  On top of the rotary, the window and the sinks.  NULL: none.
+   * (The descriptors are versioned by XTRL_ABI_VERSION, not append-only: the pointer sits here, 8-byte aligned
+   * after the two ints, and the sink fields stay the struct's last) */
+  const float* alibi_slopes;
   /* attention sinks (ABI 25): world_model['attn_num_mem_kv'] learned memory key / value rows per kv head
    * (XtrlDecodeLayer.mem_k / mem_v; no rotary) and world_model['attn_add_zero_kv'], one all-zero key /
    * value ("+ 1" in the softmax denominator).  The step-t query attends its cached keys (the window's)
@@ -508,6 +515,32 @@ int xtrl_attn_bwd_part_sink(const float* q, const float* k, const float* v, cons
                             float* dmem_k, float* dmem_v, float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv,
                             int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
                             int window, int num_mem_kv, int add_zero_kv, void* stream);
+/* The three _sink entry points with ALiBi (x-transformers alibi_pos_bias; ABI 27): alibi_slopes is a device
+ * float [H], one slope per query head (whatever Hkv is; 0 = no bias for that head), and
+ *   s_ij = scale q_i . k_j - alibi_slopes[h] (i - j)
+ * for the real keys, i and j the positions inside the episode, added before the causal, padding and window
+ * masks; the memory rows and the zero key take no bias.  The dropout keep bits are those of the _sink entry
+ * points.  The bias has no parameter and no gradient: the backward recomputes P with it, dq / dk keep
+ * their scale factor.  With slopes the kernels are the general forms (kv head mapping and window at run
+ * time, Hkv = H included) and, as for Hkv < H, there is no one-launch fused backward: n <= 128 runs the
+ * kernel pair (xtrl_attn_bwd_alibi) or the partial-workspace form (xtrl_attn_bwd_part_alibi).
+ * alibi_slopes = NULL: the _sink entry points (which call these so), bit for bit. */
+int xtrl_attn_fwd_alibi(const float* q, const float* k, const float* v, const int32_t* lens, float* o, float* lse,
+                        const float* mem_k, const float* mem_v, int b, int H, int Hkv, int n, int dh, float scale,
+                        float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, int window, int num_mem_kv,
+                        int add_zero_kv, const float* alibi_slopes, void* stream);
+int xtrl_attn_bwd_alibi(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                        const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                        const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v, float* sink_ws,
+                        int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh, float scale, float dropout_p,
+                        uint64_t seed, uint32_t offset, uint32_t sub, int window, int num_mem_kv, int add_zero_kv,
+                        const float* alibi_slopes, void* stream);
+int xtrl_attn_bwd_part_alibi(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                             const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                             float* dq_part, int64_t dq_part_floats, const float* mem_k, const float* mem_v,
+                             float* dmem_k, float* dmem_v, float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv,
+                             int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
+                             int window, int num_mem_kv, int add_zero_kv, const float* alibi_slopes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Learn-step forward / backward of WorldModelActorCritic on one minibatch, hand-scheduled (no
@@ -701,6 +734,10 @@ typedef struct XtrlTrainDesc {
   const XtrlWimgEntry* wimg_tab;
   const XtrlWimgEntry* wimg_tab_host;
   int wimg_n;
+  /* ALiBi (ABI 27), as XtrlDecodeDesc.alibi_slopes: device float [H], one slope per query head, the same
+   * for every layer; the attention runs as xtrl_attn_fwd_alibi / xtrl_attn_bwd_part_alibi on the token rows
+   * (packed rows: the distance is between positions inside the episode).  No scratch, no gradient.  NULL: none */
+  const float* alibi_slopes;
   /* attention sinks (ABI 25), as XtrlDecodeDesc: num_mem_kv memory key / value rows per kv head at
    * XtrlTrainLayer.mem_k / mem_v (their gradients land at the same offsets of grad, inside the layer's
    * bucket) and add_zero_kv; the attention runs as xtrl_attn_fwd_sink / xtrl_attn_bwd_part_sink on the

@@ -23,6 +23,13 @@
 //     philox(seed; i >> 2, 0x80000000 | m, c2, c3) >= p 2^32, c3 the call's own (byte mode: its flag set).
 //   A real key's c1 is j or 16 (j >> 6) + (j & 15) with j < n < 2^31: no real key draws from a counter
 //   with bit 31 of c1 set, and the real keys' bits do not depend on M.  The zero key's value is 0: no bit.
+// ALiBi (AttnProblem.alibi, slopes [H]): the score of row i and real key j becomes scale q_i . k_j -
+// slope[h] (i - j), i and j the positions inside the episode (the lane holds both in every score loop), added
+// before the mask select; the sinks take no bias and the keep bits do not change.  The backward kernels
+// recompute P with the same term; dS, D and the scale factors of dQ / dK are as without it (the bias has no
+// gradient).  Compile-time forms of the forward, k_attn_bwd_dkdv and k_attn_bwd_dq on top of the GQA ones
+// (which serve Hkv = H too); k_attn_bwd_fused has none.  A dead row's filled scores are all the same -max
+// whatever the bias was: k_attn_dead_fwd / k_attn_dead_bwd are unchanged.
 #include "kernels.h"
 #include "philox.h"
 
@@ -75,6 +82,9 @@ struct AttnArgs {
   float *dMKp, *dMVp;     // per-(b, h) partials [b H][M][dh]
   float *dMK, *dMV;       // [Hkv][M][dh]
   int M, Z, dm_accum;
+  // ALiBi (read by the ALIBI = true instantiations only): slope per query head [H]; the score of row i and real
+  // key j (positions inside the episode) is scale q_i . k_j - alibi[h] (i - j); the sinks take no bias
+  const float* alibi;
 };
 constexpr uint32_t SINK_C1 = 0x80000000u;   // c1 of a memory column's keep word: SINK_C1 | m
 constexpr int NO_WINDOW = 1 << 30;   // (i - j <= NO_WINDOW always holds; band tile ranges become the causal ones)
@@ -88,8 +98,11 @@ __device__ __forceinline__ int64_t ebase(const AttnArgs& a, const AttnLayout& L,
 // GQA = true (Hkv < H): the K / V base is the kv head's, in its own layout; nothing else changes
 // SINK = true (M + Z > 0): the sinks enter the softmax state before the key-tile loop (instantiations of
 // their own: the forms without sinks keep their code)
-template <int DH, bool GQA = false, bool SINK = false>
+// ALIBI = true (a.alibi set, always with GQA: the kv head mapping at run time, Hkv = H included): the
+// head's distance penalty joins each real key's score before the mask select
+template <int DH, bool GQA = false, bool SINK = false, bool ALIBI = false>
 __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
+  static_assert(GQA || !ALIBI, "the ALiBi forms take the kv head mapping at run time");
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Ks[TK][KST], Vs[TK][KST];
   __shared__ float Ps[4][16][PST];
@@ -106,6 +119,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
   const int ksi = GQA ? a.kv.si : isi;
   const int lr = lane & 15, lg = lane >> 4;
   const uint32_t off = a.offset + (uint32_t)bh;
+  const float slope = ALIBI ? a.alibi[h] : 0.f;
 
   float qa[KS];
   {
@@ -208,7 +222,9 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
       for (int sub = 0; sub < 4; ++sub) {
         const int j = kt * TK + 16 * sub + lr;
         const bool ok = (j <= i || !a.causal) && (j < len) && (i - j <= a.window);
-        sv[sub] = ok ? sacc[sub][r] * a.scale : -INFINITY;
+        float sc = sacc[sub][r] * a.scale;
+        if constexpr (ALIBI) sc -= slope * (float)(i - j);
+        sv[sub] = ok ? sc : -INFINITY;
         mx = fmaxf(mx, sv[sub]);
       }
 #pragma unroll
@@ -279,9 +295,11 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
 // ascending order, each over its query tiles as before, adding into the same dK / dV registers — a
 // fixed summation order, no atomics.  D, the dQ partials and the keep bits stay per query head.
 // GQA = false: one pass with h = the grid's head, the code of before
-template <int DH, bool DQ = false, bool WIN = true, bool GQA = false>
+// ALIBI = true (always with GQA, Hkv = H included): p is recomputed with the query head's distance penalty
+template <int DH, bool DQ = false, bool WIN = true, bool GQA = false, bool ALIBI = false>
 __global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_attn_bwd_dkdv(const AttnArgs a) {
   static_assert(WIN || !GQA, "the GQA forms take the window at run time");
+  static_assert(GQA || !ALIBI, "the ALiBi forms take the kv head mapping at run time");
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Qs[TQ][KST], dOs[TQ][KST];
   __shared__ float Ks[DQ ? TK : 1][KST];
@@ -337,6 +355,7 @@ __global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_a
       }
     }
   }
+  float slope = 0.f;   // ALIBI: the query head's, set per pass of the group loop
   int g = 0;   // GQA: the query heads, ascending; one pass each for those of this kv head
   do {
     if constexpr (GQA) {
@@ -346,6 +365,7 @@ __global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_a
       bh = b * a.H + h;
       ib = ebase(a, a.in, b) + h * a.in.sh, ob = ebase(a, a.out, b) + h * a.out.sh, gb = ebase(a, a.grad, b) + h * a.grad.sh;
       off = a.offset + (uint32_t)bh;
+      if constexpr (ALIBI) slope = a.alibi[h];
       if (DQ && j0 == 0 && len <= 0) {   // (as above, per query head)
         for (int x = tid; x < n * DH; x += 256) {
           const int i = x / DH, c = x - i * DH;
@@ -428,7 +448,9 @@ __global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_a
             const int j = j0 + 16 * w + 4 * lg + r;
             // 0 <= i - j <= W in one compare
             const bool ok = (WIN ? (unsigned)(i - j) <= (unsigned)a.window : j <= i) && (j < len) && (i < n);
-            const float p = ok ? expf(st[r] * a.scale - Ls[il]) : 0.f;
+            float sc = st[r] * a.scale;
+            if constexpr (ALIBI) sc -= slope * (float)(i - j);
+            const float p = ok ? expf(sc - Ls[il]) : 0.f;
             float z = 1.f;
             if (a.thresh8 && ok) z = (kq[r] >= a.thresh8) ? a.inv_keep : 0.f;
             else if (a.thresh && ok) z = (kq[r] >= a.thresh) ? a.inv_keep : 0.f;
@@ -534,8 +556,9 @@ __global__ __launch_bounds__(256) void k_attn_dq_reduce(const AttnArgs a, int BH
 }
 
 // ---------------------------------------------------------------------------------------------
-template <int DH, bool GQA = false>
+template <int DH, bool GQA = false, bool ALIBI = false>   // ALIBI: as k_attn_bwd_dkdv (always with GQA)
 __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
+  static_assert(GQA || !ALIBI, "the ALiBi forms take the kv head mapping at run time");
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Ks[TK][KST], Vs[TK][KST];
   __shared__ float Ds[4][16][PST];
@@ -552,6 +575,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
   const int ksi = GQA ? a.kv.si : isi;
   const int lr = lane & 15, lg = lane >> 4;
   const uint32_t off = a.offset + (uint32_t)bh;
+  const float slope = ALIBI ? a.alibi[h] : 0.f;
 
   float qa[KS], da[KS];
   {
@@ -602,7 +626,9 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
       for (int r = 0; r < 4; ++r) {
         const int i = q0 + 16 * w + 4 * lg + r;
         const bool ok = ((unsigned)(i - j) <= (unsigned)a.window) && (j < len) && (i < n);   // 0 <= i - j <= W
-        const float p = ok ? expf(s_[r] * a.scale - lse[r]) : 0.f;
+        float sc = s_[r] * a.scale;
+        if constexpr (ALIBI) sc -= slope * (float)(i - j);
+        const float p = ok ? expf(sc - lse[r]) : 0.f;
         float z = 1.f;
         if (a.thresh8 && ok) z = (qbyte(kb8, sub, r) >= a.thresh8) ? a.inv_keep : 0.f;
         else if (a.thresh && ok) z = (qword(kw, r) >= a.thresh) ? a.inv_keep : 0.f;
@@ -1031,6 +1057,8 @@ int fill_args(AttnArgs& a, const AttnProblem& p) {
   a.MV = p.mem_v;
   a.M = p.mem_kv;
   a.Z = p.zero_kv ? 1 : 0;
+  XTRL_REQUIRE(!p.alibi || p.causal, "attn: ALiBi needs causal attention");
+  a.alibi = p.alibi;   // (its forms are the GQA ones: a.Hkv = H, a.kv = in, a.kvgrad = grad above serve Hkv = H)
   return XTRL_OK;
 }
 
@@ -1086,7 +1114,17 @@ int attn_fwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   a.OGout = og;
   const bool gqa = is_gqa(p);
   dim3 grid((p.n + TQ - 1) / TQ, p.b * p.H);
-  if (attn_has_sinks(p)) {   // the sink form (one per dh: it takes the kv head mapping at run time, Hkv = H included)
+  if (p.alibi) {   // the ALiBi forms (two per dh: with and without sinks; both take the kv head mapping at run time)
+    if (attn_has_sinks(p)) {
+      if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, true, true>), grid, dim3(256), 0, s, a);
+      else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, true, true>), grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((k_attn_fwd<64, true, true, true>), grid, dim3(256), 0, s, a);
+    } else {
+      if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, false, true>), grid, dim3(256), 0, s, a);
+      else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, false, true>), grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((k_attn_fwd<64, true, false, true>), grid, dim3(256), 0, s, a);
+    }
+  } else if (attn_has_sinks(p)) {   // the sink form (one per dh: it takes the kv head mapping at run time, Hkv = H included)
     if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, true>), grid, dim3(256), 0, s, a);
     else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_attn_fwd<64, true, true>), grid, dim3(256), 0, s, a);
@@ -1124,7 +1162,27 @@ int attn_bwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   dim3 grid((p.n + TQ - 1) / TQ, p.b * p.H);
   const int64_t part_need = attn_dq_part_floats(p.b, p.H, p.n, p.dh);
   const bool gqa = is_gqa(p);
-  if (gqa) {
+  if (p.alibi) {
+    // ALiBi: the GQA forms with the bias (a.Hkv = H without grouped-query attention: a group of one query
+    // head per kv head), under GQA's rule — no one-launch fused backward, the partial-workspace form when
+    // the caller gave the workspace, else the kernel pair
+    dim3 kgrid((p.n + TK - 1) / TK, p.b * a.Hkv);
+    if (p.dh == 16 && p.dq_part && p.dq_part_floats >= part_need && attn_fused_bwd_on()) {
+      a.dQp = p.dq_part;
+      hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, true, true, true>), kgrid, dim3(256), 0, s, a);
+      const int64_t units = (int64_t)p.b * p.H * p.n * 4;
+      hipLaunchKernelGGL(k_attn_dq_reduce<16>, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, a, p.b * p.H);
+    } else if (p.dh == 16) {
+      hipLaunchKernelGGL((k_attn_bwd_dkdv<16, false, true, true, true>), kgrid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((k_attn_bwd_dq<16, true, true>), grid, dim3(256), 0, s, a);
+    } else if (p.dh == 32) {
+      hipLaunchKernelGGL((k_attn_bwd_dkdv<32, false, true, true, true>), kgrid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((k_attn_bwd_dq<32, true, true>), grid, dim3(256), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((k_attn_bwd_dkdv<64, false, true, true, true>), kgrid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((k_attn_bwd_dq<64, true, true>), grid, dim3(256), 0, s, a);
+    }
+  } else if (gqa) {
     // Hkv < H: the dK / dV grid is over the kv heads (the group loop); the dQ side stays per query head.
     // The one-launch fused backward has no group loop: short episodes take the long-episode form when
     // the caller gave the dQ partial workspace, else the kernel pair
@@ -1189,17 +1247,27 @@ AttnProblem contiguous_problem(const int32_t* lens, int b, int H, int n, int dh,
 
 }  // namespace xtrl
 
-extern "C" int xtrl_attn_fwd_sink(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
-                                  float* lse, const float* mem_k, const float* mem_v, int b, int H, int Hkv, int n,
-                                  int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
-                                  int window, int num_mem_kv, int add_zero_kv, void* stream) {
+extern "C" int xtrl_attn_fwd_alibi(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
+                                   float* lse, const float* mem_k, const float* mem_v, int b, int H, int Hkv, int n,
+                                   int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
+                                   int window, int num_mem_kv, int add_zero_kv, const float* alibi_slopes,
+                                   void* stream) {
   XTRL_REQUIRE(Hkv >= 1, "attn_fwd: kv heads %d < 1", Hkv);
   xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv);
   pr.mem_k = mem_k;
   pr.mem_v = mem_v;
   pr.mem_kv = num_mem_kv;
   pr.zero_kv = add_zero_kv;
+  pr.alibi = alibi_slopes;
   return xtrl::attn_fwd_ex(pr, q, k, v, o, lse, nullptr, nullptr, xtrl::as_stream(stream));
+}
+
+extern "C" int xtrl_attn_fwd_sink(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
+                                  float* lse, const float* mem_k, const float* mem_v, int b, int H, int Hkv, int n,
+                                  int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
+                                  int window, int num_mem_kv, int add_zero_kv, void* stream) {
+  return xtrl_attn_fwd_alibi(q, k, v, lens, o, lse, mem_k, mem_v, b, H, Hkv, n, dh, scale, dropout_p, seed, offset, sub,
+                             window, num_mem_kv, add_zero_kv, nullptr, stream);
 }
 
 extern "C" int xtrl_attn_fwd_gqa(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
@@ -1229,13 +1297,14 @@ extern "C" int64_t xtrl_attn_sink_ws_floats(int b, int H, int num_mem_kv, int dh
   return xtrl::attn_sink_ws_floats(b, H, num_mem_kv, dh);
 }
 
-extern "C" int xtrl_attn_bwd_part_sink(const float* q, const float* k, const float* v, const int32_t* lens,
-                                       const float* o, const float* lse, const float* dout, float* dq, float* dk,
-                                       float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats,
-                                       const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v,
-                                       float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh,
-                                       float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
-                                       int window, int num_mem_kv, int add_zero_kv, void* stream) {
+extern "C" int xtrl_attn_bwd_part_alibi(const float* q, const float* k, const float* v, const int32_t* lens,
+                                        const float* o, const float* lse, const float* dout, float* dq, float* dk,
+                                        float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats,
+                                        const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v,
+                                        float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh,
+                                        float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
+                                        int window, int num_mem_kv, int add_zero_kv, const float* alibi_slopes,
+                                        void* stream) {
   XTRL_REQUIRE(Hkv >= 1, "attn_bwd: kv heads %d < 1", Hkv);
   xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv);
   pr.dq_part = dq_part;
@@ -1248,7 +1317,31 @@ extern "C" int xtrl_attn_bwd_part_sink(const float* q, const float* k, const flo
   pr.dmem_v = dmem_v;
   pr.sink_ws = sink_ws;
   pr.sink_ws_floats = sink_ws_floats;
+  pr.alibi = alibi_slopes;
   return xtrl::attn_bwd_ex(pr, q, k, v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+}
+
+extern "C" int xtrl_attn_bwd_alibi(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                                   const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                                   const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v, float* sink_ws,
+                                   int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh, float scale,
+                                   float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, int window,
+                                   int num_mem_kv, int add_zero_kv, const float* alibi_slopes, void* stream) {
+  return xtrl_attn_bwd_part_alibi(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, nullptr, 0, mem_k, mem_v, dmem_k,
+                                  dmem_v, sink_ws, sink_ws_floats, b, H, Hkv, n, dh, scale, dropout_p, seed, offset,
+                                  sub, window, num_mem_kv, add_zero_kv, alibi_slopes, stream);
+}
+
+extern "C" int xtrl_attn_bwd_part_sink(const float* q, const float* k, const float* v, const int32_t* lens,
+                                       const float* o, const float* lse, const float* dout, float* dq, float* dk,
+                                       float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats,
+                                       const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v,
+                                       float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh,
+                                       float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
+                                       int window, int num_mem_kv, int add_zero_kv, void* stream) {
+  return xtrl_attn_bwd_part_alibi(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, dq_part, dq_part_floats, mem_k,
+                                  mem_v, dmem_k, dmem_v, sink_ws, sink_ws_floats, b, H, Hkv, n, dh, scale, dropout_p,
+                                  seed, offset, sub, window, num_mem_kv, add_zero_kv, nullptr, stream);
 }
 
 extern "C" int xtrl_attn_bwd_sink(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,

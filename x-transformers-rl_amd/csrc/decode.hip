@@ -365,7 +365,11 @@ __device__ __forceinline__ float sink_fold(float ts, int zero_kv, float& mx, flo
   return f;
 }
 
-template <int DH, int FJ, bool SINK = false>
+// ALiBi (ALIBI = true, D.alibi_slopes set; always on the SINK forms, which with no sink at all fold nothing —
+// factor 1, terms 0): the cached key at window-relative position j takes - slope[h] (tw - j), its distance
+// to the query at tw measured after the window's pointer shift by j_lo ((t - j_lo) - (j_abs - j_lo) = t -
+// j_abs); the new key (j = tw) and the sinks take none
+template <int DH, int FJ, bool SINK = false, bool ALIBI = false>
 __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDecodeDesc D, const XtrlDecodeLayer Ly, int layer,
                                                       int t, const FrPost fp) {
   constexpr int CK = DH <= 32 ? 128 : 64;          // keys per chunk
@@ -482,6 +486,7 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
   for (int i = 0; i < DH; ++i) qreg[i] = qs[i];
   float ts = -INFINITY;   // SINK: memory row `lane`'s score
   if constexpr (SINK) ts = sink_score<DH>(Ly.mem_k, kvh, D.num_mem_kv, lane, qreg, scale);
+  const float slope = ALIBI ? D.alibi_slopes[h] : 0.f;
   // scores, one key per lane; chunk 0 from the prefetched rows
   float mx = -INFINITY;
   for (int j0 = 0; j0 <= tw; j0 += CK) {
@@ -515,6 +520,7 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
         for (int i = 0; i < DH; ++i) s += qreg[i] * ks[i];
       }
       s *= scale;
+      if constexpr (ALIBI) s -= slope * (float)(tw - j);   // (j = tw, the new key: 0)
       if (j <= tw) {
         sc[j] = s;
         mx = fmaxf(mx, s);
@@ -1438,7 +1444,9 @@ int launch_attn_decode(const XtrlDecodeDesc* D, int l, int t, hipStream_t s, con
   if (attn_fused(D, l)) {   // one workgroup of H waves per live row
     const size_t lds = ((size_t)D->H * (D->Tmax + 3 * D->dh) + (size_t)D->H * D->d) * sizeof(float);
     const dim3 grid(D->E), blk(64 * D->H);
-    if (sinks && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    if (D->alibi_slopes && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    else if (D->alibi_slopes) hipLaunchKernelGGL((k_attn_decode<16, 1, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    else if (sinks && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
     else if (sinks) hipLaunchKernelGGL((k_attn_decode<16, 1, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
     else if (D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
     else hipLaunchKernelGGL((k_attn_decode<16, 1>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
@@ -1449,7 +1457,11 @@ int launch_attn_decode(const XtrlDecodeDesc* D, int l, int t, hipStream_t s, con
   const size_t lds = 4 * (size_t)(D->Tmax + 3 * D->dh) * sizeof(float);
   XTRL_REQUIRE(lds <= 160 * 1024, "attn_decode: Tmax %d too large for LDS", D->Tmax);
   dim3 grid((waves + 3) / 4);
-  if (sinks) {
+  if (D->alibi_slopes) {   // the ALiBi forms (on the SINK ones, with or without sinks)
+    if (D->dh == 16) hipLaunchKernelGGL((k_attn_decode<16, 0, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
+    else if (D->dh == 32) hipLaunchKernelGGL((k_attn_decode<32, 0, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
+    else hipLaunchKernelGGL((k_attn_decode<64, 0, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
+  } else if (sinks) {
     if (D->dh == 16) hipLaunchKernelGGL((k_attn_decode<16, 0, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
     else if (D->dh == 32) hipLaunchKernelGGL((k_attn_decode<32, 0, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
     else hipLaunchKernelGGL((k_attn_decode<64, 0, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
@@ -1898,8 +1910,8 @@ constexpr uint32_t HG_CANCEL = 0xFFFFFFFFu;
 // takes 4 d / Ge of the heads' hidden units and its partial of the last Linear; the partials meet
 // through k_mlp's hand-off (sc1 stores, one counter per row) and the last arriver sums them in
 // workgroup order, adds b2 and samples.  The heads are ~40 % of a row's weight bytes (C2).
-// SINK: attention sinks, as k_attn_decode<., ., true>
-template <int DH, int KP = (DH == 16 ? 2 : 1), bool SINK = false>   // KP: 64-key K passes per round trip
+// SINK: attention sinks, as k_attn_decode<., ., true>; ALIBI (always with SINK): as k_attn_decode<., ., true, true>
+template <int DH, int KP = (DH == 16 ? 2 : 1), bool SINK = false, bool ALIBI = false>   // KP: 64-key K passes per round trip
 __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, int t, int G, const HostGate hg) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ int rows_sh[EMB_MAX_E];
@@ -2116,6 +2128,7 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
         const float* kcw = Ly.k_cache + cb + (int64_t)j_lo * DH;
         const float* vcw = Ly.v_cache + cb + (int64_t)j_lo * DH;
         float* scw = sc + j_lo;
+        const float slope = ALIBI ? D.alibi_slopes[h] : 0.f;   // (the new key's score kn takes no bias)
         float mx = kn;
         for (int j0 = 0; j0 < tw; j0 += 64 * NP) {
           float4 kr[NP][F4];
@@ -2138,6 +2151,7 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
               s_ += qv.w * kr[u][i].w;
             }
             s_ *= scale;
+            if constexpr (ALIBI) s_ -= slope * (float)(tw - j);   // the distance after the shift by j_lo
             if (j < tw) {
               scw[j] = s_;
               mx = fmaxf(mx, s_);
@@ -2362,7 +2376,11 @@ int decode_step_rows(const XtrlDecodeDesc* D, int t, int max_rows, hipStream_t s
   const size_t lds = (size_t)row_lds(*D).tot * sizeof(float);
   if (hg.go) XTRL_REQUIRE(grid.x == 1 && D->act_host, "decode rows: the gated host step takes one row (E == 1) "
                                                        "and the pinned action buffer");
-  if (D->num_mem_kv > 0 || D->add_zero_kv) {   // the SINK forms
+  if (D->alibi_slopes) {   // the ALiBi forms (on the SINK ones, with or without sinks)
+    if (D->dh == 16) hipLaunchKernelGGL((k_decode_row<16, 2, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+    else if (D->dh == 32) hipLaunchKernelGGL((k_decode_row<32, 1, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+    else hipLaunchKernelGGL((k_decode_row<64, 1, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+  } else if (D->num_mem_kv > 0 || D->add_zero_kv) {   // the SINK forms
     if (D->dh == 16) hipLaunchKernelGGL((k_decode_row<16, 2, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
     else if (D->dh == 32) hipLaunchKernelGGL((k_decode_row<32, 1, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
     else hipLaunchKernelGGL((k_decode_row<64, 1, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);

@@ -245,6 +245,11 @@ struct AttnProblem {
   int dmem_accum = 0;
   float* sink_ws = nullptr;
   int64_t sink_ws_floats = 0;
+  // ALiBi (x-transformers alibi_pos_bias): slopes [H] on the device, one per query head (0: no bias for
+  // that head).  The score of query i and real key j, positions inside the episode, is
+  // scale q_i . k_j - alibi[h] (i - j), added before the masks; the sinks take no bias.  No parameter, no
+  // gradient.  NULL: none (today's kernels); set: the general forms (run-time kv head mapping and window)
+  const float* alibi = nullptr;
 };
 constexpr int kMaxMemKV = 16;   // one 16-column MFMA sub-tile
 inline bool attn_has_sinks(const AttnProblem& p) { return p.mem_kv > 0 || p.zero_kv != 0; }

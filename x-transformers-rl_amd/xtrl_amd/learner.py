@@ -60,7 +60,7 @@ XT_DEFAULTS = dict(
     attn_talking_heads=False, attn_head_scale=False, attn_sparse_topk=None, attn_num_mem_kv=0, attn_on_attn=False,
     attn_gate_value_heads=False, attn_swiglu_values=False, attn_qk_norm=False, attn_one_kv_head=False,
     attn_kv_heads=None, attn_shared_kv=False, attn_value_dim_head=None, attn_add_zero_kv=False,
-    attn_rotary_embed_values=False, attn_max_attend_past=None)
+    attn_rotary_embed_values=False, attn_max_attend_past=None, alibi_num_heads=None, alibi_learned=False)
 
 
 MAX_MEM_KV = 16   # attn_num_mem_kv: the memory rows are one 16-column MFMA sub-tile (kernels.h kMaxMemKV)
@@ -129,7 +129,11 @@ class Agent(nn.Module):
         known = {'attn_dim_head', 'heads', 'depth', 'attn_gate_values', 'add_value_residual',
                  'learned_value_residual_mix', 'ff_mult', 'ff_no_bias', 'ff_glu', 'attn_qk_norm',
                  'attn_qk_norm_scale', 'rotary_xpos', 'rotary_xpos_scale_base', 'use_rmsnorm',
-                 'attn_max_attend_past', 'attn_one_kv_head', 'attn_num_mem_kv', 'attn_add_zero_kv'}
+                 'attn_max_attend_past', 'attn_one_kv_head', 'attn_num_mem_kv', 'attn_add_zero_kv',
+                 'alibi_pos_bias', 'alibi_num_heads'}
+        if 'alibi_learned' in wm:   # (not at its default: those were dropped above)
+            raise NotImplementedError('alibi_learned is not supported by the MI355X decoder: the ALiBi slopes are the '
+                                      'fixed geometric sequence (alibi_pos_bias), without parameters')
         unknown = set(wm) - known
         if unknown:
             # (world_model['attn_kv_heads'] stays among the refused options, as before grouped-query attention
@@ -172,6 +176,20 @@ class Agent(nn.Module):
             raise NotImplementedError('attn_num_mem_kv > 0 together with attn_qk_norm is not supported: x-transformers '
                                       'normalises and rescales the memory keys there (attn_add_zero_kv with '
                                       'attn_qk_norm is fine)')
+        # ALiBi (x-transformers alibi_pos_bias / alibi_num_heads): the first alibi_num_heads heads (None: all)
+        # subtract slope[h] (i - j) from their scores, on top of the rotary (ops.alibi_slopes)
+        alibi = wm.get('alibi_pos_bias', False)
+        if not isinstance(alibi, (bool, np.bool_)):
+            raise ValueError(f'alibi_pos_bias must be a bool, not {alibi!r}')
+        alibi_heads = wm.get('alibi_num_heads')
+        if alibi_heads is not None:
+            if not alibi:
+                raise ValueError('alibi_num_heads needs alibi_pos_bias=True')
+            if isinstance(alibi_heads, bool) or not isinstance(alibi_heads, (int, np.integer)) or \
+                    not 1 <= alibi_heads <= heads:
+                raise ValueError(f'alibi_num_heads must be an int from 1 to heads = {heads}, or None (every head), '
+                                 f'not {alibi_heads!r}')
+        alibi_heads = (int(alibi_heads) if alibi_heads is not None else int(heads)) if alibi else 0
         self.seed = int(seed)
         self.evolutionary = evolutionary
         self.evolve_every, self.evolve_after_step = evolve_every, evolve_after_step
@@ -190,7 +208,7 @@ class Agent(nn.Module):
                         rotary_xpos=bool(wm.get('rotary_xpos', False)),
                         xpos_scale_base=float(wm.get('rotary_xpos_scale_base', 512.)),
                         rotary_abs_rollout=rotary_abs_rollout, attn_window=int(window or 0), kv_heads=kv_heads,
-                        num_mem_kv=int(num_mem_kv), add_zero_kv=bool(add_zero_kv),
+                        num_mem_kv=int(num_mem_kv), add_zero_kv=bool(add_zero_kv), alibi_heads=alibi_heads,
                         hl_reduction_mean=hl_reduction_mean, hl_sigma_ratio=hl_sigma_ratio)
         self.cfg = c
         # the learn step without the minibatch's padding (XtrlTrainDesc.packed): exact only with the
@@ -211,6 +229,8 @@ class Agent(nn.Module):
             if c.num_mem_kv or c.add_zero_kv:
                 raise NotImplementedError('the fractal policy body has no attention sinks: leave attn_num_mem_kv at 0 '
                                           'and attn_add_zero_kv at False')
+            if c.alibi_heads:
+                raise NotImplementedError('the fractal policy body has no ALiBi: leave alibi_pos_bias at False')
             if c.gate_values or c.value_residual or c.ff_no_bias or c.ff_glu or c.qk_norm or c.rotary_xpos or c.rms_norm:
                 raise NotImplementedError('the fractal policy body has no gated values / value residual / bias-free or '
                                           'GLU feed-forward / qk norm / xPos rotary / RMSNorm: set attn_gate_values / '

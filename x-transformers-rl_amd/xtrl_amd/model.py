@@ -56,6 +56,7 @@ class ModelConfig:
     kv_heads: int = 0                    # kv heads (GQA: Agent kv_heads / attn_one_kv_head); 0 or heads: multi-head
     num_mem_kv: int = 0                  # x-transformers attn_num_mem_kv: learned memory key / value rows per kv head
     add_zero_kv: bool = False            # x-transformers attn_add_zero_kv: one all-zero key / value ("+ 1" softmax)
+    alibi_heads: int = 0                 # x-transformers alibi_pos_bias: heads with an ALiBi slope (alibi_num_heads); 0: off
     rotary_abs_rollout: bool = False     # decision log: reference semantics = rotary position 0 in rollout
     hl_reduction_mean: bool = True       # decision log: hl-gauss-pytorch default reduction
     hl_sigma_ratio: float = 2.0
@@ -224,6 +225,10 @@ class WorldModelActorCritic(nn.Module):
         self.register_buffer('hl_support', support, persistent=False)
         self.register_buffer('hl_centers', (support[:-1] + support[1:]) / 2, persistent=False)
         self.hl_sigma = c.hl_sigma_ratio * (hi - lo) / c.num_bins
+        # ALiBi slopes [heads] (heads past alibi_heads: 0).  Not persistent: no state-dict entry, so checkpoints
+        # interchange with the reference's (whose slopes buffer is non-persistent too) and with a model without
+        self.register_buffer('alibi_slopes', ops.alibi_slopes(c.heads, c.alibi_heads) if c.alibi_heads else None,
+                             persistent=False)
 
     # ---- pieces shared with the rollout weight packing -----------------------------------------
     def blocks(self):
@@ -377,7 +382,7 @@ class WorldModelActorCritic(nn.Module):
             k = torch.cat((k[..., :rot] * cos * xk + _rotate_half(k[..., :rot]) * sin * xk, k[..., rot:]), dim=-1)
             o = ops.attention(q, k, v, lens, scale, p_drop, attn_seed, attn_offset, li, window=c.attn_window,
                               mem_k=getattr(blk, 'mem_k', None), mem_v=getattr(blk, 'mem_v', None),
-                              add_zero_kv=c.add_zero_kv)
+                              add_zero_kv=c.add_zero_kv, alibi_slopes=self.alibi_slopes)
             o = o.permute(0, 2, 1, 3).reshape(b, n, I)
             if gate_pre is not None:
                 o = o * gate_pre.sigmoid()

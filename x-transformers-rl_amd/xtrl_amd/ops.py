@@ -221,11 +221,13 @@ class AttentionFn(torch.autograd.Function):
     [b][H][n][dh]; k, v are [b][Hkv][n][dh] with Hkv dividing H (grouped-query attention: query head h
     reads kv head kv_head_index(H, Hkv)[h]; dk, dv come back [b][Hkv][n][dh], summed over each group).
     Attention sinks: mem_k, mem_v [Hkv][M][dh] (or None) and add_zero_kv join every row's softmax
-    (include/xtrl_hip.h, xtrl_attn_fwd_sink); their gradients come back with dq, dk, dv."""
+    (include/xtrl_hip.h, xtrl_attn_fwd_sink); their gradients come back with dq, dk, dv.
+    ALiBi: alibi_slopes [H] fp32 (or None) subtracts slope[h] (i - j) from the real keys' scores
+    (xtrl_attn_fwd_alibi; no gradient).  Without slopes the calls are the _sink ones."""
 
     @staticmethod
     def forward(ctx, q, k, v, lens, scale, dropout_p, seed, offset, sub, window=0, mem_k=None, mem_v=None,
-                add_zero_kv=False):
+                add_zero_kv=False, alibi_slopes=None):
         lib = L.lib()
         b, H, n, dh = q.shape
         Hkv = k.shape[1]
@@ -240,13 +242,20 @@ class AttentionFn(torch.autograd.Function):
             if t is not None:
                 _f32c(t)
                 assert t.shape == (Hkv, M, dh), f'memory key / values must be [Hkv][M][dh], not {tuple(t.shape)}'
+        if alibi_slopes is not None:
+            _f32c(alibi_slopes)
+            assert alibi_slopes.shape == (H,), f'alibi_slopes must be [heads], not {tuple(alibi_slopes.shape)}'
         o = torch.empty_like(q)
         lse = torch.empty(b, H, n, device=q.device, dtype=torch.float32)
-        L.check(lib.xtrl_attn_fwd_sink(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse),
-                                       L.ptr(mem_k) if M else None, L.ptr(mem_v) if M else None, b, H, Hkv, n, dh,
-                                       float(scale), float(dropout_p), int(seed), int(offset), int(sub), int(window),
-                                       M, int(bool(add_zero_kv)), L.stream()), 'attn_fwd')
+        args = (L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(mem_k) if M else None,
+                L.ptr(mem_v) if M else None, b, H, Hkv, n, dh, float(scale), float(dropout_p), int(seed), int(offset),
+                int(sub), int(window), M, int(bool(add_zero_kv)))
+        if alibi_slopes is not None:
+            L.check(lib.xtrl_attn_fwd_alibi(*args, L.ptr(alibi_slopes), L.stream()), 'attn_fwd')
+        else:
+            L.check(lib.xtrl_attn_fwd_sink(*args, L.stream()), 'attn_fwd')
         ctx.save_for_backward(q, k, v, lens, o, lse, *((mem_k, mem_v) if M else ()))
+        ctx.alibi = alibi_slopes   # (no gradient: not a saved tensor of the graph)
         ctx.cfg = (float(scale), float(dropout_p), int(seed), int(offset), int(sub), int(window), M,
                    int(bool(add_zero_kv)))
         return o
@@ -268,24 +277,46 @@ class AttentionFn(torch.autograd.Function):
             ws_floats = int(lib.xtrl_attn_sink_ws_floats(b, H, M, dh))
             ws = torch.empty(ws_floats, device=q.device, dtype=torch.float32)
         pm = lambda t: L.ptr(t) if t is not None else None
-        L.check(lib.xtrl_attn_bwd_sink(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do),
-                                       L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(delta), pm(mem_k), pm(mem_v), pm(dmk),
-                                       pm(dmv), pm(ws), ws_floats, b, H, k.shape[1], n, dh, scale, p, seed, offset, sub,
-                                       window, M, Z, L.stream()), 'attn_bwd')
-        return dq, dk, dv, None, None, None, None, None, None, None, dmk, dmv, None
+        args = (L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do), L.ptr(dq), L.ptr(dk),
+                L.ptr(dv), L.ptr(delta), pm(mem_k), pm(mem_v), pm(dmk), pm(dmv), pm(ws), ws_floats, b, H, k.shape[1],
+                n, dh, scale, p, seed, offset, sub, window, M, Z)
+        if ctx.alibi is not None:
+            L.check(lib.xtrl_attn_bwd_alibi(*args, L.ptr(ctx.alibi), L.stream()), 'attn_bwd')
+        else:
+            L.check(lib.xtrl_attn_bwd_sink(*args, L.stream()), 'attn_bwd')
+        return dq, dk, dv, None, None, None, None, None, None, None, dmk, dmv, None, None
+
+
+def alibi_slopes(heads, alibi_heads=None):
+    """[heads] fp32 ALiBi slopes (the ALiBi paper's rule, as x-transformers' AlibiPositionalBias): the first
+    ``alibi_heads`` heads (None: all) take the geometric sequence, the others 0 (no bias).  For a power of two
+    n the sequence is s^(k + 1), s = 2^(-8 / n); otherwise, with c the largest power of two <= n, that of c
+    followed by every other element of that of 2c.  Computed in fp64 and rounded to fp32."""
+    A = heads if alibi_heads is None else int(alibi_heads)
+    assert 1 <= A <= heads, f'alibi heads {A} outside [1, {heads}]'
+
+    def pow2(n):
+        return [2.0 ** (-8.0 * (k + 1) / n) for k in range(n)]
+
+    c = 1 << (A.bit_length() - 1)
+    sl = pow2(A) if c == A else pow2(c) + pow2(2 * c)[0::2][:A - c]
+    return torch.tensor(sl + [0.0] * (heads - A), dtype=torch.float64).to(torch.float32)
 
 
 def attention(q, k, v, lens, scale, dropout_p=0., seed=0, offset=0, sub=0, window=0, mem_k=None, mem_v=None,
-              add_zero_kv=False):
+              add_zero_kv=False, alibi_slopes=None):
     """``offset`` / ``sub``: the dropout stream (Philox c2 base and c3 sub-index = decoder layer);
     ``window`` > 0: query i sees key j only if i - j <= window (x-transformers max_attend_past).
     k, v with fewer heads than q (a divisor): grouped-query attention (x-transformers attn_kv_heads).
     ``mem_k`` / ``mem_v`` [Hkv][M][dh] and ``add_zero_kv``: attention sinks every row sees (x-transformers
-    attn_num_mem_kv / attn_add_zero_kv)."""
+    attn_num_mem_kv / attn_add_zero_kv).  ``alibi_slopes`` [H] fp32: the ALiBi distance penalty
+    - slope[h] (i - j) on the real keys' scores (x-transformers alibi_pos_bias; `alibi_slopes()` above)."""
     if mem_k is not None:
         mem_k, mem_v = mem_k.contiguous(), mem_v.contiguous()
+    if alibi_slopes is not None:
+        alibi_slopes = alibi_slopes.detach().contiguous()
     return AttentionFn.apply(q.contiguous(), k.contiguous(), v.contiguous(), lens, scale, dropout_p, seed, offset,
-                             sub, window, mem_k, mem_v, add_zero_kv)
+                             sub, window, mem_k, mem_v, add_zero_kv, alibi_slopes)
 
 
 # --------------------------------------------------------------------------------------------

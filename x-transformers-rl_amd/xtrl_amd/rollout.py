@@ -180,6 +180,10 @@ class RolloutEngine:
         D.Hkv = self.Hkv                                     # kv heads (grouped-query attention; = H without)
         # attention sinks: memory rows per kv head (XtrlDecodeLayer.mem_k / mem_v) and the zero key
         D.num_mem_kv, D.add_zero_kv = int(getattr(c, 'num_mem_kv', 0)), int(bool(getattr(c, 'add_zero_kv', False)))
+        # ALiBi: the slopes [H] (the model's rule; the deploy forward runs through this engine too)
+        if int(getattr(c, 'alibi_heads', 0)):
+            self.alibi_slopes = ops.alibi_slopes(c.heads, c.alibi_heads).to(self.dev)
+            D.alibi_slopes = self.alibi_slopes.data_ptr()
         D.sim_mode, D.hazard_log2, D.rs_eps = self.sim_mode, hazard_log2, 1e-5
         if clamp is not None:
             D.clamp_lo, D.clamp_hi, D.has_clamp = float(clamp[0]), float(clamp[1]), 1
@@ -694,6 +698,7 @@ class FractalRolloutEngine(RolloutEngine):
         self.desc.attn_window = 0   # (the fractal body has no sliding window)
         self.desc.Hkv = 0           # (nor grouped-query attention)
         self.desc.num_mem_kv = self.desc.add_zero_kv = 0   # (nor attention sinks)
+        self.desc.alibi_slopes = None   # (nor ALiBi)
         Lv = self.levels
         levels = (L.FractalLevel * Lv)()
         names = [n for n, _ in L.FractalLevel._fields_]

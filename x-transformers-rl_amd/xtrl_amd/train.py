@@ -196,6 +196,11 @@ class FusedTrainStep:
         if D.num_mem_kv:
             self.sink_ws = E(int(L.lib().xtrl_attn_sink_ws_floats(b_max, H, D.num_mem_kv, dh)))
             D.sink_ws, D.sink_ws_floats = self.sink_ws.data_ptr(), self.sink_ws.numel()
+        # ALiBi: the slopes [H] (the model's rule, a copy of this step's own: the descriptor keeps its address)
+        if int(getattr(c, 'alibi_heads', 0)):
+            from . import ops
+            self.alibi_slopes = ops.alibi_slopes(H, c.alibi_heads).to(dev)
+            D.alibi_slopes = self.alibi_slopes.data_ptr()
         D.inv_freq = self.inv_freq.data_ptr()
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
@@ -407,6 +412,7 @@ class FractalTrainStep(FusedTrainStep):
         D.attn_window = 0   # (the fractal body has no sliding window)
         D.Hkv = 0           # (nor grouped-query attention)
         D.num_mem_kv = D.add_zero_kv = 0   # (nor attention sinks)
+        D.alibi_slopes = None              # (nor ALiBi)
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
         D.part_floats = self.buf['part'].numel()
