@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 27
+#define XTRL_ABI_VERSION 28
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -580,6 +580,7 @@ typedef struct XtrlTrainLayer {
 } XtrlTrainLayer;
 
 typedef struct XtrlWimgEntry XtrlWimgEntry;   /* a pre-split weight image, below */
+typedef struct XtrlWfragEntry XtrlWfragEntry; /* a fragment-order weight image, below */
 
 typedef struct XtrlTrainDesc {
   int b, n, S, A, d, L, H, dh, ff, B, in_dim, n_out, G;
@@ -738,6 +739,18 @@ typedef struct XtrlTrainDesc {
    * for every layer; the attention runs as xtrl_attn_fwd_alibi / xtrl_attn_bwd_part_alibi on the token rows
    * (packed rows: the distance is between positions inside the episode).  No scratch, no gradient.  NULL: none */
   const float* alibi_slopes;
+  /* fragment-order weight images (ABI 28; optional, wfrag NULL = off): the split-bf16 pieces of the weights
+   * the 64 x 256 LayerNorm-epilogue GEMMs (d > 128) read as B, in the order one consumer wave loads its MFMA
+   * fragments, so those launches keep B out of LDS: each consumer wave loads its own 64 columns straight
+   * from the image (L2) into registers, one slab ahead, and the producers split A only.  Table, arena and
+   * life cycle as for wimg (xtrl_train_wfrag_plan; rebuilt by xtrl_train_forward as its first launch, reused
+   * by the backward).  A launch that also has an LDS-DMA image (wimg) takes that one.  (Versioned by
+   * XTRL_ABI_VERSION, not append-only: the sink fields stay the struct's last, as in XtrlDecodeDesc) */
+  void* wfrag;
+  int64_t wfrag_bytes;
+  const XtrlWfragEntry* wfrag_tab;
+  const XtrlWfragEntry* wfrag_tab_host;
+  int wfrag_n;
   /* attention sinks (ABI 25), as XtrlDecodeDesc: num_mem_kv memory key / value rows per kv head at
    * XtrlTrainLayer.mem_k / mem_v (their gradients land at the same offsets of grad, inside the layer's
    * bucket) and add_zero_kv; the attention runs as xtrl_attn_fwd_sink / xtrl_attn_bwd_part_sink on the
@@ -771,6 +784,30 @@ int xtrl_wimg_build(const float* flat, const XtrlWimgEntry* tab_host, const Xtrl
 
 /* GEMM launches of this process that read B from an image so far (host counter; tests) */
 int64_t xtrl_wimg_launch_count(void);
+
+/* One fragment-order weight image: the B operand (N <= 256 columns, reduction length K; w_off, ld and
+ * trans_b as in XtrlWimgEntry) padded with zeros to 256 columns and ceil(K / 32) slabs of 32, 6 bytes per
+ * element, no padding.  Unit (w, s) -- the 64-column block w of one consumer wave, slab s -- is the
+ * contiguous XTRL_WFRAG_UNIT_BYTES at img_off + (w ceil(K / 32) + s) * XTRL_WFRAG_UNIT_BYTES: 12 blocks of
+ * 1 KiB, block ((st * 3 + p) * 2 + j) for k16 step st, piece p (hi, mid, lo as in XtrlWimgEntry) and
+ * 32-column tile j.  A block is 64 lanes x 16 bytes: lane l holds piece p of B[32 s + 16 st + 8 (l >> 5) + i]
+ * [64 w + 32 j + (l & 31)], i = 0 .. 7 -- the bf16x8 B fragment of one 32x32x16 MFMA.  blk0: the image's
+ * first unit in the build launch. */
+struct XtrlWfragEntry {
+  int64_t w_off;
+  int64_t img_off;
+  int N, K, ld, trans_b, blk0, pad_;
+};
+#define XTRL_WFRAG_UNIT_BYTES (12 * 1024)
+/* the fragment images a learn step on `desc` reads (host-only; as xtrl_train_wimg_plan): per block w_out,
+ * w_ff2, w_ff1^T, w_proj^T, then the embed columns of w_h1^T; none unless the fused LayerNorm path runs
+ * on 64 x 256 tiles (128 < d <= 256) */
+int xtrl_train_wfrag_plan(const XtrlTrainDesc* desc, XtrlWfragEntry* tab, int cap, int64_t* bytes);
+/* builds every image of a table (tab_dev: its device copy) from `flat` into the arena, one launch */
+int xtrl_wfrag_build(const float* flat, const XtrlWfragEntry* tab_host, const XtrlWfragEntry* tab_dev, int n,
+                     void* arena, int64_t arena_bytes, void* stream);
+/* GEMM launches of this process that read B from a fragment image so far (host counter; tests) */
+int64_t xtrl_wfrag_launch_count(void);
 
 int xtrl_train_forward(const XtrlTrainDesc* desc, void* stream);
 int xtrl_train_backward(const XtrlTrainDesc* desc, void* stream);

@@ -47,7 +47,8 @@ extern "C" int64_t xtrl_struct_size(const char* name) {
                {"XtrlTrainDesc", sizeof(XtrlTrainDesc)},     {"XtrlBatchDesc", sizeof(XtrlBatchDesc)},
                {"XtrlLossDesc", sizeof(XtrlLossDesc)},       {"XtrlFractalLevel", sizeof(XtrlFractalLevel)},
                {"XtrlFractalDesc", sizeof(XtrlFractalDesc)},     {"XtrlFractalTrainLevel", sizeof(XtrlFractalTrainLevel)},
-               {"XtrlFractalTrainDesc", sizeof(XtrlFractalTrainDesc)}, {"XtrlWimgEntry", sizeof(XtrlWimgEntry)}};
+               {"XtrlFractalTrainDesc", sizeof(XtrlFractalTrainDesc)}, {"XtrlWimgEntry", sizeof(XtrlWimgEntry)},
+               {"XtrlWfragEntry", sizeof(XtrlWfragEntry)}};
   for (const auto& s : sizes)
     if (name && strcmp(name, s.name) == 0) return s.size;
   return -1;

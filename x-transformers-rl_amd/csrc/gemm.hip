@@ -965,22 +965,34 @@ __device__ int g_ws_mode;   // 1: consumers skip the MFMAs; 2: producers skip lo
 // Measured slower than the register-staged B in every instantiation at C3 (a slab's DMA is issued and
 // waited for inside one step: no LDS for a third B buffer), so callers pass no image
 // unless asked to (XTRL_WIMG=1 on the Python side).
+//
+// WF (64 x 256 LayerNorm-epilogue tiles; B a weight with a fragment-order image, GemmArgs::wfrag): B stays
+// out of LDS.  In this tile the four consumer waves sit 1 x 4, each reads its own 64 columns of B, so LDS
+// staging buys B no reuse.  Each consumer wave loads the 12 fragments (2 k16 steps x 3 pieces x 2 column
+// tiles, 16 bytes per lane each) of slab t + 1 from the image (L2) into registers before slab t's MFMAs
+// and feeds them to the MFMAs directly; it reads only A fragments from LDS.  The producers load, split
+// and store A only, the piece images shrink to A's 64 rows, the LayerNorm tile keeps its own size.  The
+// image is zero past N and K (no clamp, no KT mask for B).  Same pieces, same MFMA order: bit-identical.
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-template <bool TA, bool TB, int EPI, bool RES, int BM = 128, int BN = 128, bool KT = false, bool WI = false>
+template <bool TA, bool TB, int EPI, bool RES, int BM = 128, int BN = 128, bool KT = false, bool WI = false,
+          bool WF = false>
 __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
   constexpr int BK = 32, XRS = BK + 8, NP = 256, TM = 2, TN = 2, WN = BN / 64;
   constexpr bool LNE = (EPI == EPI_RES_LN || EPI == EPI_LN_BWD || EPI == EPI_LN_BWD2);
   static_assert(!WI || !TA, "weight images feed B of the A \"N\" launches");
+  static_assert(!WF || (!TA && !WI && LNE && BM == 64 && BN == 256), "fragment images: the 64 x 256 LayerNorm tiles");
   static_assert(XTRL_WIMG_TILE_BYTES(BN) == 3 * BN * XRS * 2, "image tile = the B part of a piece image");
   constexpr int A_F4 = BM * BK / 4 / NP, B_F4 = BN * BK / 4 / NP;   // float4 per producer thread per slab
-  constexpr int IMG = 3 * (BM + BN) * XRS;                           // bf16 per piece image
+  constexpr int IMG = 3 * (BM + (WF ? 0 : BN)) * XRS;                // bf16 per piece image (WF: A only)
   static_assert((BM == 128 && BN == 128) || (BM == 64 && BN == 256), "tile 128 x 128 or 64 x 256");
   static_assert(!TA || A_F4 == 4, "A \"T\": one 4 x 4 transposed group per producer thread");
   static_assert(!TB || B_F4 % 4 == 0, "B \"T\": whole 4 x 4 transposed groups per producer thread");
   constexpr int LDT = BN + 4;                                        // LN epilogue: tile rows in LDS (floats)
-  static_assert(!LNE || (BM * LDT + 8 * BN) * 4 <= 2 * IMG * 2, "LN tile exceeds the piece images");
-  __shared__ __attribute__((aligned(16))) __bf16 smem[2 * IMG];
+  static_assert(WF || !LNE || (BM * LDT + 8 * BN) * 4 <= 2 * IMG * 2, "LN tile exceeds the piece images");
+  constexpr int SMEM = WF ? (BM * LDT + 8 * BN) * 2 : 2 * IMG;       // bf16 (WF: the LN tile is the larger)
+  static_assert(SMEM >= 2 * IMG, "two piece images");
+  __shared__ __attribute__((aligned(16))) __bf16 smem[SMEM];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool producer = wave >= 4;
@@ -1045,7 +1057,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
         ra[S][i] = ld_t(Ab, a.lda, k0 + 4 * kq + i, m0 + 4 * q, M);
       }
     }
-    if constexpr (!WI) {
+    if constexpr (!WI && !WF) {
 #pragma unroll
       for (int i = 0; i < B_F4; ++i) {
         if constexpr (!TB) {
@@ -1115,7 +1127,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
         }
       }
     }
-    if constexpr (WI) {   // B arrives by dma_b
+    if constexpr (WI || WF) {   // B arrives by dma_b / goes from its fragment image to the consumers' registers
     } else if constexpr (!TB) {
 #pragma unroll
       for (int i = 0; i < B_F4; ++i) {
@@ -1180,6 +1192,49 @@ __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
 #pragma unroll
           for (int j = 0; j < TN; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[pb][PA[t]][i], bv[pb][PB[t]][j], acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  // WF: this wave's B fragments of one slab, [k16 step][piece][column tile], straight from the image;
+  // two sets, slab t + 1 in flight while slab t is multiplied (a slab past the last repeats it, unread)
+  bf16x8 bf[2][BK / 16][3][TN];
+  auto ldb = [&](auto S, int kt) {
+    if constexpr (WF) {
+      const int w = __builtin_amdgcn_readfirstlane(wn);
+      const char* src = static_cast<const char*>(a.wfrag) +
+                        ((int64_t)w * nk + min(kt, nk - 1)) * XTRL_WFRAG_UNIT_BYTES + lane * 16;
+#pragma unroll
+      for (int i = 0; i < 12; ++i)
+        bf[decltype(S)::value][i / 6][(i / 2) % 3][i % 2] = *reinterpret_cast<const bf16x8*>(src + i * 1024);
+    }
+  };
+  auto compute_f = [&](const __bf16* xa, auto S) {   // `compute` with B from bf[S]
+    const int xi = wm * 32 * TM + (lane & 31), xk = 8 * (lane >> 5);
+    bf16x8 av[2][3][TM];
+    auto rd = [&](int buf, int st) {
+      auto ra_ = [&](int pc) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+          av[buf][pc][i] = *reinterpret_cast<const bf16x8*>(xa + (pc * BM + xi + 32 * i) * XRS + 16 * st + xk);
+      };
+      ra_(2); ra_(0); ra_(1);
+    };
+    rd(0, 0);
+#pragma unroll
+    for (int st = 0; st < BK / 16; ++st) {
+      const int pb = st & 1;
+      if (st + 1 < BK / 16) rd(pb ^ 1, st + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+      for (int t = 0; t < 6; ++t)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[pb][PA[t]][i], bf[decltype(S)::value][st][PB[t]][j],
+                                                                acc[i][j], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -1272,6 +1327,26 @@ __global__ __launch_bounds__(512, 1) void k_gemm_ws(const GemmArgs a) {
       }
     }
     if constexpr (!LNE) return;
+  } else if constexpr (WF) {
+    // the producers' barrier sequence; in step t the loads of slab t + 1 go out before slab t's MFMAs
+    // (no branch around a load or a product: an odd nk ends with one step and the producers' spare barrier)
+    ldb(I0{}, 0);
+    __syncthreads();
+    auto cstep = [&](auto S, auto Sn, int t) {
+      ldb(Sn, t + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      compute_f(smem + (t & 1) * IMG, S);
+      __syncthreads();
+    };
+    int t = 0;
+    for (; t + 1 < nk; t += 2) {
+      cstep(I0{}, I1{}, t);
+      cstep(I1{}, I0{}, t + 1);
+    }
+    if (t < nk) {
+      cstep(I0{}, I1{}, t);
+      __syncthreads();
+    }
   } else {
     __syncthreads();
     for (int t = 0; t < nsteps; ++t) {
@@ -1478,6 +1553,7 @@ bool ws_ok(const GemmArgs& a, bool ta, bool ln) {
   return wgs <= 256 && (a.kspan > 0 ? a.kspan : a.K) >= (ta ? 64 : 512);
 }
 
+int64_t g_wfrag_launches = 0;  // fragment-image launches so far (xtrl_wfrag_launch_count)
 int64_t g_wimg_launches = 0;   // image-fed launches so far (xtrl_wimg_launch_count: tests check the path is taken)
 
 bool wimg_on() {   // XTRL_WIMG=0: no pre-split weight images (A/B experiments)
@@ -1505,6 +1581,25 @@ void launch_ws(const GemmArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((k_gemm_ws<TA, TB, EPI, RES, BM, BN, KT>), grid, dim3(512), 0, s, r);
 }
 
+// the 64 x 256 LayerNorm-epilogue launch: B from its LDS-DMA image if the launch has one, else from its
+// fragment image (KT only for a partial last slab), else register-staged (KT_PLAIN: that kernel's KT)
+template <bool TB, int EPI, bool RES, bool KT_PLAIN>
+void launch_ln256(const GemmArgs& a, hipStream_t s) {
+  const bool wi = a.wimg && a.wimg_bn == 256 && wimg_on();
+  if (a.wfrag && !wi && a.kspan == 0) {
+    dim3 grid(1, (a.M + 63) / 64, 1);
+    GemmArgs r = a;
+    r.xcd_remap = grid.y % 8 == 0 ? 1 : 0;
+    ++g_wfrag_launches;
+    if (a.K % 32 != 0)
+      hipLaunchKernelGGL((k_gemm_ws<false, TB, EPI, RES, 64, 256, true, false, true>), grid, dim3(512), 0, s, r);
+    else
+      hipLaunchKernelGGL((k_gemm_ws<false, TB, EPI, RES, 64, 256, false, false, true>), grid, dim3(512), 0, s, r);
+    return;
+  }
+  launch_ws<false, TB, EPI, RES, 64, 256, KT_PLAIN>(a, s);
+}
+
 // the LayerNorm-epilogue GEMMs: one column tile per row (N <= 256), 128-row tiles up to N = 128,
 // 64 x 256 above; K a multiple of 4 (KT masks a partial last slab)
 int ln_gemm_run(const GemmArgs& a, int trans_a, int trans_b, int epi, bool vec, hipStream_t s) {
@@ -1522,13 +1617,13 @@ int ln_gemm_run(const GemmArgs& a, int trans_a, int trans_b, int epi, bool vec, 
       if (kt) launch_ws<false, false, EPI_RES_LN, true, 128, 128, true>(a, s);
       else launch_ws<false, false, EPI_RES_LN, true, 128, 128, false>(a, s);
     } else {
-      if (kt) launch_ws<false, false, EPI_RES_LN, true, 64, 256, true>(a, s);
-      else launch_ws<false, false, EPI_RES_LN, true, 64, 256, false>(a, s);
+      if (kt) launch_ln256<false, EPI_RES_LN, true, true>(a, s);
+      else launch_ln256<false, EPI_RES_LN, true, false>(a, s);
     }
   } else if (epi == EPI_LN_BWD) {
     XTRL_REQUIRE(trans_b && !res && a.ln_x && a.ln_part, "gemm: LayerNorm-backward epilogue arguments");
     if (narrow) launch_ws<false, true, EPI_LN_BWD, false, 128, 128, true>(a, s);
-    else launch_ws<false, true, EPI_LN_BWD, false, 64, 256, true>(a, s);
+    else launch_ln256<true, EPI_LN_BWD, false, true>(a, s);
   } else {
     XTRL_REQUIRE(trans_b && !res && a.ln_x && a.ln_part && (!a.ln_gpre || ((uintptr_t)a.ln_gpre & 15u) == 0) &&
                      a.ln_ldg % 4 == 0 &&
@@ -1537,7 +1632,7 @@ int ln_gemm_run(const GemmArgs& a, int trans_a, int trans_b, int epi, bool vec, 
                      a.ldc == a.N,
                  "gemm: post-norm LayerNorm-backward epilogue arguments");
     if (narrow) launch_ws<false, true, EPI_LN_BWD2, false, 128, 128, true>(a, s);
-    else launch_ws<false, true, EPI_LN_BWD2, false, 64, 256, true>(a, s);
+    else launch_ln256<true, EPI_LN_BWD2, false, true>(a, s);
   }
   XTRL_LAUNCHED("gemm_ln");
   return XTRL_OK;
@@ -2100,7 +2195,88 @@ int wimg_build(const float* flat, const XtrlWimgEntry* tab_host, const XtrlWimgE
   return XTRL_OK;
 }
 
+// ---- fragment-order weight images (XtrlWfragEntry, include/xtrl_hip.h; k_gemm_ws WF) -----------------
+// One workgroup per unit (64-column block w, 32-deep slab s) of any entry: thread (st, j, l) takes the 8
+// consecutive k of one column that lane l of a consumer wave feeds to the MFMAs of k16 step st, column
+// tile j, splits them with split3 and stores the three 16-byte fragments; columns past N and k past K
+// are stored as zeros.
+namespace {
+__global__ __launch_bounds__(256) void k_wfrag_build(const float* __restrict__ flat, const XtrlWfragEntry* __restrict__ tab,
+                                                     int n, char* __restrict__ arena) {
+  int e = 0;
+  while (e + 1 < n && tab[e + 1].blk0 <= (int)blockIdx.x) ++e;
+  const XtrlWfragEntry E = tab[e];
+  const int nkt = (E.K + 31) / 32, blk = (int)blockIdx.x - E.blk0, w = blk / nkt, s = blk % nkt;
+  const int t = threadIdx.x, l = t & 63, j = (t >> 6) & 1, st = t >> 7;
+  const int col = 64 * w + 32 * j + (l & 31), k0 = 32 * s + 16 * st + 8 * (l >> 5);
+  const float* W = flat + E.w_off;
+  float v[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const bool ok = col < E.N && k0 + c < E.K;
+    const int64_t at = E.trans_b ? (int64_t)(k0 + c) * E.ld + col : (int64_t)col * E.ld + k0 + c;
+    const float x = W[ok ? at : 0];   // (every load in bounds, the value selected afterwards)
+    v[c] = ok ? x : 0.f;
+  }
+  bf16x4 h[2], m[2], lo[2];
+  split3(make_float4(v[0], v[1], v[2], v[3]), h[0], m[0], lo[0]);
+  split3(make_float4(v[4], v[5], v[6], v[7]), h[1], m[1], lo[1]);
+  char* out = arena + E.img_off + (int64_t)blk * XTRL_WFRAG_UNIT_BYTES + l * 16;
+  auto store = [&](int pc, const bf16x4 (&x)[2]) {
+    bf16x4* q = reinterpret_cast<bf16x4*>(out + ((st * 3 + pc) * 2 + j) * 1024);
+    q[0] = x[0];
+    q[1] = x[1];
+  };
+  store(0, h);
+  store(1, m);
+  store(2, lo);
+}
+}  // namespace
+
+bool wfrag_applies(int N, int epi) {
+  return (epi == EPI_RES_LN || epi == EPI_LN_BWD || epi == EPI_LN_BWD2) && N > 128 && N <= 256;
+}
+
+void wfrag_find(GemmArgs& g, int trans_b, int epi, const float* flat, const XtrlWfragEntry* tab, int n,
+                const void* arena) {
+  if (!tab || !arena || n <= 0 || !wfrag_applies(g.N, epi)) return;
+  for (int i = 0; i < n; ++i) {
+    const XtrlWfragEntry& E = tab[i];
+    if (flat + E.w_off == g.B && E.trans_b == trans_b && E.N == g.N && E.K == g.K && E.ld == g.ldb) {
+      g.wfrag = static_cast<const char*>(arena) + E.img_off;
+      return;
+    }
+  }
+}
+
+int wfrag_build(const float* flat, const XtrlWfragEntry* tab_host, const XtrlWfragEntry* tab_dev, int n, void* arena,
+                int64_t arena_bytes, hipStream_t s) {
+  XTRL_REQUIRE(flat && tab_host && tab_dev && arena && n > 0, "wfrag: null table / arena");
+  XTRL_REQUIRE(((uintptr_t)arena & 15u) == 0, "wfrag: the arena must be 16-byte aligned");
+  int blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    const XtrlWfragEntry& E = tab_host[i];
+    XTRL_REQUIRE(E.N > 0 && E.N <= 256 && E.K > 0 && E.w_off >= 0 && E.img_off >= 0 && E.img_off % 16 == 0 &&
+                     E.blk0 == blocks && (E.trans_b == 0 || E.trans_b == 1) && E.ld >= (E.trans_b ? E.N : E.K),
+                 "wfrag: bad table entry %d", i);
+    const int64_t units = 4 * (int64_t)((E.K + 31) / 32);
+    XTRL_REQUIRE(E.img_off + units * XTRL_WFRAG_UNIT_BYTES <= arena_bytes,
+                 "wfrag: entry %d ends past the arena (%lld bytes)", i, (long long)arena_bytes);
+    blocks += (int)units;
+  }
+  hipLaunchKernelGGL(k_wfrag_build, dim3(blocks), dim3(256), 0, s, flat, tab_dev, n, static_cast<char*>(arena));
+  XTRL_LAUNCHED("wfrag_build");
+  return XTRL_OK;
+}
+
 }  // namespace xtrl
+
+extern "C" int64_t xtrl_wfrag_launch_count(void) { return xtrl::g_wfrag_launches; }
+
+extern "C" int xtrl_wfrag_build(const float* flat, const XtrlWfragEntry* tab_host, const XtrlWfragEntry* tab_dev, int n,
+                                void* arena, int64_t arena_bytes, void* stream) {
+  return xtrl::wfrag_build(flat, tab_host, tab_dev, n, arena, arena_bytes, xtrl::as_stream(stream));
+}
 
 extern "C" int64_t xtrl_wimg_launch_count(void) { return xtrl::g_wimg_launches; }
 

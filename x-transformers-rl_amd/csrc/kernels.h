@@ -90,7 +90,16 @@ struct GemmArgs {
   // NULL, or a launch that does not go to that kernel: B is read from `B` as ever
   const void* wimg = nullptr;
   int wimg_bn = 0;
+  // fragment-order image of B (wfrag_find; XtrlWfragEntry): the 64 x 256 LayerNorm-epilogue launches load
+  // B's MFMA fragments from it straight into the consumers' registers.  wimg, when also set, wins
+  const void* wfrag = nullptr;
 };
+// the fragment image of the B operand (B, ldb, N, K, trans_b) in a table of n entries over `flat`, if any
+void wfrag_find(GemmArgs& g, int trans_b, int epi, const float* flat, const XtrlWfragEntry* tab, int n,
+                const void* arena);
+bool wfrag_applies(int N, int epi);   // the launch goes to a 64 x 256 LayerNorm-epilogue tile
+int wfrag_build(const float* flat, const XtrlWfragEntry* tab_host, const XtrlWfragEntry* tab_dev, int n, void* arena,
+                int64_t arena_bytes, hipStream_t s);
 // the image of the B operand (B, ldb, N, K, trans_b) in a table of n entries over `flat`, if it has one
 // whose tiles suit the kernel this GEMM goes to (epi: a LayerNorm epilogue's tile is gemm_ln_rows' partner)
 void wimg_find(GemmArgs& g, int trans_b, int epi, const float* flat, const XtrlWimgEntry* tab, int n,

@@ -905,6 +905,7 @@ struct Ctx {
   // B's pre-split image, when the step has one for this weight view (XtrlTrainDesc.wimg)
   void img(GemmArgs& g, int trans_b, int epi) const {
     wimg_find(g, trans_b, epi, D->flat, D->wimg_tab_host, D->wimg_n, D->wimg);
+    wfrag_find(g, trans_b, epi, D->flat, D->wfrag_tab_host, D->wfrag_n, D->wfrag);
   }
 };
 
@@ -1508,6 +1509,9 @@ int train_forward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
   // reused by this step's backward (XTRL_WIMG=0: none; the lookups then find nothing either)
   if (D->wimg && D->wimg_tab && D->wimg_tab_host && D->wimg_n > 0 && wimg_enabled())
     if ((rc = wimg_build(D->flat, D->wimg_tab_host, D->wimg_tab, D->wimg_n, D->wimg, D->wimg_bytes, s))) return rc;
+  // the fragment-order images of the 64 x 256 LayerNorm-epilogue GEMMs' weights, likewise
+  if (D->wfrag && D->wfrag_tab && D->wfrag_tab_host && D->wfrag_n > 0)
+    if ((rc = wfrag_build(D->flat, D->wfrag_tab_host, D->wfrag_tab, D->wfrag_n, D->wfrag, D->wfrag_bytes, s))) return rc;
   // embeddings
   if (D->evolutionary) {
     hipLaunchKernelGGL(k_latent_embed, dim3(blocks(D->b * d, 256)), dim3(256), 0, s, D->latent, c.P(D->w_lat),
@@ -2228,6 +2232,37 @@ extern "C" int xtrl_train_wimg_plan(const XtrlTrainDesc* D, XtrlWimgEntry* tab, 
     }
     add(D->w_h1, 1, d, 4 * d, D->in_dim, xtrl::EPI_LN_BWD2);
     if (D->w_h1 >= 0) add(D->w_h1 + d, 1, D->in_dim - d, 4 * d, D->in_dim, xtrl::EPI_NONE);
+  }
+  if (bytes) *bytes = at;
+  return n;
+}
+
+// The weight views the 64 x 256 LayerNorm-epilogue launches read as B (128 < d <= 256, fused LayerNorms):
+// per block the out-projection and FF2 forward, FF1 and the q|k|v projection as input gradients; the embed
+// columns of the actor | critic first layer as the final norm's input gradient.
+extern "C" int xtrl_train_wfrag_plan(const XtrlTrainDesc* D, XtrlWfragEntry* tab, int cap, int64_t* bytes) {
+  int n = 0, blk = 0;
+  int64_t at = 0;
+  auto add = [&](int64_t w_off, int trans_b, int N, int K, int ld) {
+    if (w_off < 0 || N <= 0 || K <= 0) return;
+    XtrlWfragEntry E{};
+    E.w_off = w_off; E.img_off = at; E.N = N; E.K = K; E.ld = ld; E.trans_b = trans_b; E.blk0 = blk;
+    const int units = 4 * ((K + 31) / 32);
+    if (tab && n < cap) tab[n] = E;
+    ++n;
+    blk += units;
+    at += (int64_t)units * XTRL_WFRAG_UNIT_BYTES;
+  };
+  if (D && D->layers && D->L > 0 && xtrl::ln_fusable(D) && xtrl::wfrag_applies(D->d, xtrl::EPI_RES_LN)) {
+    const int d = D->d, I = D->H * D->dh, f1 = D->ff_glu ? 2 * D->ff : D->ff;
+    for (int li = 0; li < D->L; ++li) {
+      const XtrlTrainLayer& Ly = D->layers[li];
+      add(Ly.w_out, 0, d, I, I);
+      add(Ly.w_ff2, 0, d, D->ff, D->ff);
+      add(Ly.w_ff1, 1, d, f1, d);
+      add(Ly.w_proj, 1, d, Ly.n_qkv, d);
+    }
+    add(D->w_h1, 1, d, 4 * d, D->in_dim);
   }
   if (bytes) *bytes = at;
   return n;

@@ -13,7 +13,7 @@ from pathlib import Path
 import torch   # noqa: F401  (load torch's HIP runtime first so the library binds to the same one)
 
 LIB_PATH = Path(os.environ.get('XTRL_LIB', Path(__file__).resolve().parent / 'libxtrl_hip.so'))   # override: A/B experiments
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 P = C.c_void_p
 I32, I64, U32, U64, F32 = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
@@ -102,6 +102,15 @@ def wimg_tile_bytes(bn: int) -> int:
     return 3 * bn * WIMG_XRS * 2
 
 
+class WfragEntry(C.Structure):
+    """One fragment-order weight image (XtrlWfragEntry): the B operand view and its place in the arena."""
+    _fields_ = [('w_off', I64), ('img_off', I64), ('N', I32), ('K', I32), ('ld', I32), ('trans_b', I32), ('blk0', I32),
+                ('pad_', I32)]
+
+
+WFRAG_UNIT_BYTES = 12 * 1024   # one (64-column block, 32-deep slab) unit: 12 fragment blocks of 1 KiB
+
+
 class TrainDesc(C.Structure):
     _fields_ = ([(n, I32) for n in ('b', 'n', 'S', 'A', 'd', 'L', 'H', 'dh', 'ff', 'B', 'in_dim', 'n_out', 'G',
                                     'continuous', 'evolutionary', 'gate_values', 'rot_dim')]
@@ -125,6 +134,8 @@ class TrainDesc(C.Structure):
                    ('packed', I32), ('ep_off', P), ('pack_ws', P), ('pack_ws_floats', I64), ('attn_window', I32),
                    ('Hkv', I32), ('wimg', P), ('wimg_bytes', I64), ('wimg_tab', P),
                    ('wimg_tab_host', C.POINTER(WimgEntry)), ('wimg_n', I32), ('alibi_slopes', P),
+                   ('wfrag', P), ('wfrag_bytes', I64), ('wfrag_tab', P), ('wfrag_tab_host', C.POINTER(WfragEntry)),
+                   ('wfrag_n', I32),
                    ('num_mem_kv', I32), ('add_zero_kv', I32), ('sink_ws', P), ('sink_ws_floats', I64)])
 
 
@@ -222,6 +233,9 @@ SIGNATURES = {
     'xtrl_train_part_floats': (C.c_int64, [I32, I32, I32, I32]),
     'xtrl_train_wimg_plan': (I32, [C.POINTER(TrainDesc), C.POINTER(WimgEntry), I32, C.POINTER(I64)]),
     'xtrl_wimg_launch_count': (I64, []),
+    'xtrl_train_wfrag_plan': (I32, [C.POINTER(TrainDesc), C.POINTER(WfragEntry), I32, C.POINTER(I64)]),
+    'xtrl_wfrag_launch_count': (I64, []),
+    'xtrl_wfrag_build': (I32, [P, C.POINTER(WfragEntry), P, I32, P, I64, P]),
     'xtrl_wimg_build': (I32, [P, C.POINTER(WimgEntry), P, I32, P, I64, P]),
     'xtrl_minibatch_gather': (I32, [C.POINTER(BatchDesc), P]),
     'xtrl_rsnorm_update': (I32, [P, P, P, I32, I32, P]),
@@ -242,7 +256,7 @@ STRUCTS = {'XtrlDecodeLayer': DecodeLayer, 'XtrlRngState': RngState, 'XtrlDecode
            'XtrlTrainLayer': TrainLayer, 'XtrlTrainDesc': TrainDesc, 'XtrlBatchDesc': BatchDesc,
            'XtrlLossDesc': LossDesc, 'XtrlFractalLevel': FractalLevel, 'XtrlFractalDesc': FractalDesc,
            'XtrlFractalTrainLevel': FractalTrainLevel, 'XtrlFractalTrainDesc': FractalTrainDesc,
-           'XtrlWimgEntry': WimgEntry}
+           'XtrlWimgEntry': WimgEntry, 'XtrlWfragEntry': WfragEntry}
 
 _lib = None
 

@@ -78,6 +78,20 @@ def _alloc_wimg(D, dev):
     return dict(tab=tab, tab_dev=tab_dev, arena=arena)
 
 
+def _alloc_wfrag(D, dev):
+    """The arena and table of the fragment-order weight images (XtrlTrainDesc.wfrag), as _alloc_wimg.  None
+    when the step reads none (no fused LayerNorm path on 64 x 256 tiles)."""
+    nbytes = C.c_int64(0)
+    n = int(L.lib().xtrl_train_wfrag_plan(C.byref(D), None, 0, C.byref(nbytes)))
+    if n <= 0 or nbytes.value <= 0:
+        return None
+    tab = (L.WfragEntry * n)()
+    L.lib().xtrl_train_wfrag_plan(C.byref(D), tab, n, C.byref(nbytes))
+    arena = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+    return dict(tab=tab, tab_dev=tab_dev, arena=arena)
+
+
 def _heads_desc(D, c, flat):
     """Offsets of the heads every policy body shares (xtrl.py:533-557, fractal_rl.py:586-619)."""
     off = lambda n: _off(flat, n)
@@ -216,6 +230,25 @@ class FusedTrainStep:
         self.wimg = None
         if WIMG_DEFAULT:
             self.use_weight_images(True)
+        # fragment-order weight images: on by default where the library plans any (the decoder body's
+        # 64 x 256 LayerNorm-epilogue GEMMs load B's fragments from them)
+        self.wfrag = None
+        self.use_weight_fragments(True)
+
+    def use_weight_fragments(self, on: bool):
+        """Fragment-order weight images on / off for the following steps (off: the descriptor without their
+        arena, the register-staged kernels).  The arena and the table are allocated on first use."""
+        D = self.D
+        if not on or isinstance(self, FractalTrainStep):   # (the fractal step plans no images)
+            D.wfrag, D.wfrag_bytes, D.wfrag_tab, D.wfrag_tab_host, D.wfrag_n = None, 0, None, None, 0
+            return
+        if self.wfrag is None:
+            self.wfrag = _alloc_wfrag(D, self.dev)
+        w = self.wfrag
+        if w is not None:
+            D.wfrag, D.wfrag_bytes = w['arena'].data_ptr(), w['arena'].numel()
+            D.wfrag_tab, D.wfrag_tab_host, D.wfrag_n = w['tab_dev'].data_ptr(), \
+                C.cast(w['tab'], C.POINTER(L.WfragEntry)), len(w['tab'])
 
     def use_weight_images(self, on: bool):
         """Pre-split weight images on / off for the following steps (off: the descriptor without its arena —
