@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 28
+#define XTRL_ABI_VERSION 29
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -255,6 +255,12 @@ typedef struct XtrlDecodeDesc {
    * (The descriptors are versioned by XTRL_ABI_VERSION, not append-only: the pointer sits here, 8-byte aligned
    * after the two ints, and the sink fields stay the struct's last) */
   const float* alibi_slopes;
+  /* logit soft-clamp (ABI 29): world_model['attn_softclamp_logits'] with attn_logit_softclamp_value = c
+   * (x-transformers Attend softclamp_logits).  Every score of the step -- the cached keys' after their ALiBi
+   * term, the new key's and the memory rows' -- becomes c tanh(score / c) before the softmax; the zero key's
+   * 0 stays 0.  On top of the rotary, the window, the sinks, ALiBi and qk-norm (the score's scale is
+   * attn_scale then).  No parameter.  0: off */
+  float attn_softclamp;
   /* attention sinks (ABI 25): world_model['attn_num_mem_kv'] learned memory key / value rows per kv head
    * (XtrlDecodeLayer.mem_k / mem_v; no rotary) and world_model['attn_add_zero_kv'], one all-zero key /
    * value ("+ 1" in the softmax denominator).  The step-t query attends its cached keys (the window's)
@@ -541,6 +547,35 @@ int xtrl_attn_bwd_part_alibi(const float* q, const float* k, const float* v, con
                              float* dmem_k, float* dmem_v, float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv,
                              int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
                              int window, int num_mem_kv, int add_zero_kv, const float* alibi_slopes, void* stream);
+/* The three _alibi entry points with the logit soft-clamp (x-transformers attn_softclamp_logits /
+ * attn_logit_softclamp_value; ABI 29): with softclamp = c > 0 and x_ij the score above (the ALiBi term
+ * included when there are slopes),
+ *   s_ij = c tanh(x_ij / c)
+ * for the real keys and the memory columns (which take no bias), applied before the causal, padding and
+ * window masks; the zero key's score stays 0, the dropout keep bits and the dead rows of a window without
+ * sinks do not change, lse is the log-sum-exp of the clamped scores.  The backward recomputes t = tanh(x / c)
+ * with the score and multiplies dS by 1 - t^2 before dq, dk and dmem_k (same scale factors); dv and dmem_v
+ * are as without the clamp.  With softclamp > 0 the kernels are the general forms (kv head mapping and
+ * window at run time; alibi_slopes may be NULL) and, as for ALiBi, there is no one-launch fused backward.
+ * softclamp < 0 or not finite: XTRL_E_ARG, nothing launched.  softclamp = 0: the _alibi entry points (which
+ * call these so), bit for bit. */
+int xtrl_attn_fwd_softclamp(const float* q, const float* k, const float* v, const int32_t* lens, float* o, float* lse,
+                            const float* mem_k, const float* mem_v, int b, int H, int Hkv, int n, int dh, float scale,
+                            float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub, int window, int num_mem_kv,
+                            int add_zero_kv, const float* alibi_slopes, float softclamp, void* stream);
+int xtrl_attn_bwd_softclamp(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                            const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                            const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v, float* sink_ws,
+                            int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh, float scale, float dropout_p,
+                            uint64_t seed, uint32_t offset, uint32_t sub, int window, int num_mem_kv, int add_zero_kv,
+                            const float* alibi_slopes, float softclamp, void* stream);
+int xtrl_attn_bwd_part_softclamp(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,
+                                 const float* lse, const float* dout, float* dq, float* dk, float* dv, float* delta_ws,
+                                 float* dq_part, int64_t dq_part_floats, const float* mem_k, const float* mem_v,
+                                 float* dmem_k, float* dmem_v, float* sink_ws, int64_t sink_ws_floats, int b, int H,
+                                 int Hkv, int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset,
+                                 uint32_t sub, int window, int num_mem_kv, int add_zero_kv, const float* alibi_slopes,
+                                 float softclamp, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Learn-step forward / backward of WorldModelActorCritic on one minibatch, hand-scheduled (no
@@ -751,6 +786,10 @@ typedef struct XtrlTrainDesc {
   const XtrlWfragEntry* wfrag_tab;
   const XtrlWfragEntry* wfrag_tab_host;
   int wfrag_n;
+  /* logit soft-clamp (ABI 29), as XtrlDecodeDesc.attn_softclamp: c > 0 clamps the real keys' and the memory
+   * columns' scores to c tanh(score / c) in every layer; the attention runs as xtrl_attn_fwd_softclamp /
+   * xtrl_attn_bwd_part_softclamp on the token rows.  No scratch, no parameter.  0: off */
+  float attn_softclamp;
   /* attention sinks (ABI 25), as XtrlDecodeDesc: num_mem_kv memory key / value rows per kv head at
    * XtrlTrainLayer.mem_k / mem_v (their gradients land at the same offsets of grad, inside the layer's
    * bucket) and add_zero_kv; the attention runs as xtrl_attn_fwd_sink / xtrl_attn_bwd_part_sink on the

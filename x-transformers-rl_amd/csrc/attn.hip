@@ -30,6 +30,17 @@
 // gradient).  Compile-time forms of the forward, k_attn_bwd_dkdv and k_attn_bwd_dq on top of the GQA ones
 // (which serve Hkv = H too); k_attn_bwd_fused has none.  A dead row's filled scores are all the same -max
 // whatever the bias was: k_attn_dead_fwd / k_attn_dead_bwd are unchanged.
+// Logit soft-clamp (AttnProblem.softclamp = c > 0, x-transformers attn_softclamp_logits): with x the score
+// above (bias included), s = c tanh(x / c) for the real keys and the memory columns, before the mask
+// select; the zero key's 0 stays 0 and the keep bits do not change.  lse is that of the clamped scores.  The
+// backward kernels recompute t = tanh(x / c) in the expression that forms s, so P is that of the forward,
+// and hand on dX = dS (1 - t^2) where they handed on dS: dQ, dK and dmem_k take it with their scale factors,
+// dV and dmem_v do not change.  Compile-time CAP forms on top of the ALiBi ones (the slope is 0 when there
+// are no slopes), and of k_attn_sink_bwd; k_attn_bwd_fused has none.  tanhf, not 1 - 2 / (1 + e^2y): at c = 50
+// the arguments are near 0.02 and the absolute error of t is multiplied by c.  A dead row's filled scores
+// are the same -max whatever the clamp did: k_attn_dead_fwd / k_attn_dead_bwd are unchanged.
+#include <cmath>
+
 #include "kernels.h"
 #include "philox.h"
 
@@ -85,6 +96,8 @@ struct AttnArgs {
   // ALiBi (read by the ALIBI = true instantiations only): slope per query head [H]; the score of row i and real
   // key j (positions inside the episode) is scale q_i . k_j - alibi[h] (i - j); the sinks take no bias
   const float* alibi;
+  // logit soft-clamp (read by the CAP = true instantiations only): c and 1 / c
+  float cap, inv_cap;
 };
 constexpr uint32_t SINK_C1 = 0x80000000u;   // c1 of a memory column's keep word: SINK_C1 | m
 constexpr int NO_WINDOW = 1 << 30;   // (i - j <= NO_WINDOW always holds; band tile ranges become the causal ones)
@@ -100,9 +113,12 @@ __device__ __forceinline__ int64_t ebase(const AttnArgs& a, const AttnLayout& L,
 // their own: the forms without sinks keep their code)
 // ALIBI = true (a.alibi set, always with GQA: the kv head mapping at run time, Hkv = H included): the
 // head's distance penalty joins each real key's score before the mask select
-template <int DH, bool GQA = false, bool SINK = false, bool ALIBI = false>
+// CAP = true (a.cap > 0, always with ALIBI, whose slope is 0 when a.alibi is NULL): the real keys' and the
+// memory columns' scores become cap tanh(score / cap) before the mask select
+template <int DH, bool GQA = false, bool SINK = false, bool ALIBI = false, bool CAP = false>
 __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
   static_assert(GQA || !ALIBI, "the ALiBi forms take the kv head mapping at run time");
+  static_assert(ALIBI || !CAP, "the soft-clamp forms are the ALiBi-capable ones");
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Ks[TK][KST], Vs[TK][KST];
   __shared__ float Ps[4][16][PST];
@@ -119,7 +135,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
   const int ksi = GQA ? a.kv.si : isi;
   const int lr = lane & 15, lg = lane >> 4;
   const uint32_t off = a.offset + (uint32_t)bh;
-  const float slope = ALIBI ? a.alibi[h] : 0.f;
+  const float slope = ALIBI ? ((CAP && !a.alibi) ? 0.f : a.alibi[h]) : 0.f;
 
   float qa[KS];
   {
@@ -161,7 +177,9 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
       if (a.thresh) kw = philox4x32_10((uint32_t)((q0 + 16 * w + 4 * lg) >> 2), SINK_C1 | (uint32_t)lr, off, a.c3, a.seed);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float sv = lr < a.M ? sacc[r] * a.scale : -INFINITY;
+        float ms = sacc[r] * a.scale;
+        if constexpr (CAP) ms = a.cap * tanhf(ms * a.inv_cap);
+        const float sv = lr < a.M ? ms : -INFINITY;
         float mx = sv;
 #pragma unroll
         for (int o2 = 1; o2 < 16; o2 <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o2, 64));
@@ -224,6 +242,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
         const bool ok = (j <= i || !a.causal) && (j < len) && (i - j <= a.window);
         float sc = sacc[sub][r] * a.scale;
         if constexpr (ALIBI) sc -= slope * (float)(i - j);
+        if constexpr (CAP) sc = a.cap * tanhf(sc * a.inv_cap);
         sv[sub] = ok ? sc : -INFINITY;
         mx = fmaxf(mx, sv[sub]);
       }
@@ -296,10 +315,13 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const AttnArgs a) {
 // fixed summation order, no atomics.  D, the dQ partials and the keep bits stay per query head.
 // GQA = false: one pass with h = the grid's head, the code of before
 // ALIBI = true (always with GQA, Hkv = H included): p is recomputed with the query head's distance penalty
-template <int DH, bool DQ = false, bool WIN = true, bool GQA = false, bool ALIBI = false>
+// CAP = true (always with ALIBI; the slope is 0 when a.alibi is NULL): p is recomputed from cap tanh(score /
+// cap) and the dS image that feeds dK (and the folded dQ) carries the factor 1 - tanh^2; dV takes P~ as before
+template <int DH, bool DQ = false, bool WIN = true, bool GQA = false, bool ALIBI = false, bool CAP = false>
 __global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_attn_bwd_dkdv(const AttnArgs a) {
   static_assert(WIN || !GQA, "the GQA forms take the window at run time");
   static_assert(GQA || !ALIBI, "the ALiBi forms take the kv head mapping at run time");
+  static_assert(ALIBI || !CAP, "the soft-clamp forms are the ALiBi-capable ones");
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Qs[TQ][KST], dOs[TQ][KST];
   __shared__ float Ks[DQ ? TK : 1][KST];
@@ -365,7 +387,7 @@ __global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_a
       bh = b * a.H + h;
       ib = ebase(a, a.in, b) + h * a.in.sh, ob = ebase(a, a.out, b) + h * a.out.sh, gb = ebase(a, a.grad, b) + h * a.grad.sh;
       off = a.offset + (uint32_t)bh;
-      if constexpr (ALIBI) slope = a.alibi[h];
+      if constexpr (ALIBI) slope = (CAP && !a.alibi) ? 0.f : a.alibi[h];
       if (DQ && j0 == 0 && len <= 0) {   // (as above, per query head)
         for (int x = tid; x < n * DH; x += 256) {
           const int i = x / DH, c = x - i * DH;
@@ -450,12 +472,18 @@ __global__ __launch_bounds__(256, DH == 16 ? ((DQ || WIN) ? 3 : 4) : 1) void k_a
             const bool ok = (WIN ? (unsigned)(i - j) <= (unsigned)a.window : j <= i) && (j < len) && (i < n);
             float sc = st[r] * a.scale;
             if constexpr (ALIBI) sc -= slope * (float)(i - j);
+            float dt = 1.f;   // CAP: d s / d x = 1 - tanh^2(x / cap)
+            if constexpr (CAP) {
+              const float t = tanhf(sc * a.inv_cap);
+              sc = a.cap * t;
+              dt = 1.f - t * t;
+            }
             const float p = ok ? expf(sc - Ls[il]) : 0.f;
             float z = 1.f;
             if (a.thresh8 && ok) z = (kq[r] >= a.thresh8) ? a.inv_keep : 0.f;
             else if (a.thresh && ok) z = (kq[r] >= a.thresh) ? a.inv_keep : 0.f;
             Ps[w][4 * lg + r][il] = p * z;
-            dsr[sub][r] = p * (dpt[r] * z - Dls[il]);
+            dsr[sub][r] = CAP ? p * (dpt[r] * z - Dls[il]) * dt : p * (dpt[r] * z - Dls[il]);
           }
         }
         wave_sync();
@@ -556,9 +584,11 @@ __global__ __launch_bounds__(256) void k_attn_dq_reduce(const AttnArgs a, int BH
 }
 
 // ---------------------------------------------------------------------------------------------
-template <int DH, bool GQA = false, bool ALIBI = false>   // ALIBI: as k_attn_bwd_dkdv (always with GQA)
+// ALIBI, CAP: as k_attn_bwd_dkdv (ALIBI always with GQA, CAP always with ALIBI)
+template <int DH, bool GQA = false, bool ALIBI = false, bool CAP = false>
 __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
   static_assert(GQA || !ALIBI, "the ALiBi forms take the kv head mapping at run time");
+  static_assert(ALIBI || !CAP, "the soft-clamp forms are the ALiBi-capable ones");
   constexpr int KS = DH / 4, ND = DH / 16, KST = DH + 2;
   __shared__ float Ks[TK][KST], Vs[TK][KST];
   __shared__ float Ds[4][16][PST];
@@ -575,7 +605,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
   const int ksi = GQA ? a.kv.si : isi;
   const int lr = lane & 15, lg = lane >> 4;
   const uint32_t off = a.offset + (uint32_t)bh;
-  const float slope = ALIBI ? a.alibi[h] : 0.f;
+  const float slope = ALIBI ? ((CAP && !a.alibi) ? 0.f : a.alibi[h]) : 0.f;
 
   float qa[KS], da[KS];
   {
@@ -628,11 +658,17 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnArgs a) {
         const bool ok = ((unsigned)(i - j) <= (unsigned)a.window) && (j < len) && (i < n);   // 0 <= i - j <= W
         float sc = s_[r] * a.scale;
         if constexpr (ALIBI) sc -= slope * (float)(i - j);
+        float dt = 1.f;   // CAP: d s / d x = 1 - tanh^2(x / cap)
+        if constexpr (CAP) {
+          const float t = tanhf(sc * a.inv_cap);
+          sc = a.cap * t;
+          dt = 1.f - t * t;
+        }
         const float p = ok ? expf(sc - lse[r]) : 0.f;
         float z = 1.f;
         if (a.thresh8 && ok) z = (qbyte(kb8, sub, r) >= a.thresh8) ? a.inv_keep : 0.f;
         else if (a.thresh && ok) z = (qword(kw, r) >= a.thresh) ? a.inv_keep : 0.f;
-        Ds[w][4 * lg + r][jl] = p * (dp[r] * z - dl[r]);
+        Ds[w][4 * lg + r][jl] = CAP ? p * (dp[r] * z - dl[r]) * dt : p * (dp[r] * z - dl[r]);
       }
     }
     wave_sync();
@@ -908,8 +944,10 @@ __global__ __launch_bounds__(256) void k_attn_dead_bwd(const AttnArgs a) {
 // sum_i P~_im dO_i[c].  The rows are all the step holds: n (padded layout) or min(len, n) (packed).
 // k_attn_sink_reduce sums the partials over b and over a kv head's query heads in ascending order: no
 // atomics, the same bits every run.  (The zero key has no gradient of its own: it is in lse.)
+// CAP = true (a.cap > 0): P_im is that of the clamped score cap tanh(scale q_i . mem_k / cap) and the dS that
+// feeds dq and dmem_k carries 1 - tanh^2; P~ (dmem_v) does not change
 constexpr int SB_ROWS = 256, SB_ST = kMaxMemKV + 1;
-template <int DH>
+template <int DH, bool CAP = false>
 __global__ __launch_bounds__(256) void k_attn_sink_bwd(const AttnArgs a) {
   constexpr int EU = kMaxMemKV * DH / 256;   // (m, c) elements per thread
   __shared__ float mk[kMaxMemKV][DH], mv[kMaxMemKV][DH];
@@ -954,10 +992,16 @@ __global__ __launch_bounds__(256) void k_attn_sink_bwd(const AttnArgs a) {
           t += qr[c] * mk[m][c];
           gd += dor[c] * mv[m][c];
         }
-        const float p = expf(t * a.scale - lse);
+        float sc = t * a.scale, dt = 1.f;
+        if constexpr (CAP) {
+          const float th = tanhf(sc * a.inv_cap);
+          sc = a.cap * th;
+          dt = 1.f - th * th;
+        }
+        const float p = expf(sc - lse);
         float z = 1.f;
         if (a.thresh) z = keep_word(a.seed, off, a.c3, i, (int)(SINK_C1 | (uint32_t)m)) >= a.thresh ? a.inv_keep : 0.f;
-        const float ds = p * (gd * z - dsum);
+        const float ds = CAP ? p * (gd * z - dsum) * dt : p * (gd * z - dsum);
         dSs[tid][m] = ds;
         Pds[tid][m] = p * z;
 #pragma unroll
@@ -1059,6 +1103,11 @@ int fill_args(AttnArgs& a, const AttnProblem& p) {
   a.Z = p.zero_kv ? 1 : 0;
   XTRL_REQUIRE(!p.alibi || p.causal, "attn: ALiBi needs causal attention");
   a.alibi = p.alibi;   // (its forms are the GQA ones: a.Hkv = H, a.kv = in, a.kvgrad = grad above serve Hkv = H)
+  XTRL_REQUIRE(p.softclamp >= 0.f && std::isfinite(p.softclamp),
+               "attn: softclamp %g is negative or not finite (0 = off)", (double)p.softclamp);
+  XTRL_REQUIRE(p.softclamp == 0.f || p.causal, "attn: the logit soft-clamp needs causal attention");
+  a.cap = p.softclamp;   // (its forms are the ALiBi ones, a.alibi NULL included)
+  a.inv_cap = p.softclamp > 0.f ? 1.f / p.softclamp : 0.f;
   return XTRL_OK;
 }
 
@@ -1074,7 +1123,11 @@ int sink_bwd(AttnArgs& a, const AttnProblem& p, hipStream_t s) {
   a.dMK = p.dmem_k;
   a.dMV = p.dmem_v;
   a.dm_accum = p.dmem_accum;
-  if (p.dh == 16) hipLaunchKernelGGL(k_attn_sink_bwd<16>, dim3(p.b * p.H), dim3(256), 0, s, a);
+  if (p.softclamp > 0.f) {
+    if (p.dh == 16) hipLaunchKernelGGL((k_attn_sink_bwd<16, true>), dim3(p.b * p.H), dim3(256), 0, s, a);
+    else if (p.dh == 32) hipLaunchKernelGGL((k_attn_sink_bwd<32, true>), dim3(p.b * p.H), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_sink_bwd<64, true>), dim3(p.b * p.H), dim3(256), 0, s, a);
+  } else if (p.dh == 16) hipLaunchKernelGGL(k_attn_sink_bwd<16>, dim3(p.b * p.H), dim3(256), 0, s, a);
   else if (p.dh == 32) hipLaunchKernelGGL(k_attn_sink_bwd<32>, dim3(p.b * p.H), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_attn_sink_bwd<64>, dim3(p.b * p.H), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_attn_sink_reduce, dim3((a.Hkv * p.mem_kv * p.dh + 255) / 256), dim3(256), 0, s, a, p.b, p.dh);
@@ -1114,7 +1167,17 @@ int attn_fwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   a.OGout = og;
   const bool gqa = is_gqa(p);
   dim3 grid((p.n + TQ - 1) / TQ, p.b * p.H);
-  if (p.alibi) {   // the ALiBi forms (two per dh: with and without sinks; both take the kv head mapping at run time)
+  if (p.softclamp > 0.f) {   // the soft-clamp forms (the ALiBi ones plus the clamp; slopes or none)
+    if (attn_has_sinks(p)) {
+      if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, true, true, true>), grid, dim3(256), 0, s, a);
+      else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, true, true, true>), grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((k_attn_fwd<64, true, true, true, true>), grid, dim3(256), 0, s, a);
+    } else {
+      if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, false, true, true>), grid, dim3(256), 0, s, a);
+      else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, false, true, true>), grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((k_attn_fwd<64, true, false, true, true>), grid, dim3(256), 0, s, a);
+    }
+  } else if (p.alibi) {   // the ALiBi forms (two per dh: with and without sinks; both take the kv head mapping at run time)
     if (attn_has_sinks(p)) {
       if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, true, true>), grid, dim3(256), 0, s, a);
       else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, true, true>), grid, dim3(256), 0, s, a);
@@ -1162,7 +1225,25 @@ int attn_bwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   dim3 grid((p.n + TQ - 1) / TQ, p.b * p.H);
   const int64_t part_need = attn_dq_part_floats(p.b, p.H, p.n, p.dh);
   const bool gqa = is_gqa(p);
-  if (p.alibi) {
+  if (p.softclamp > 0.f) {
+    // soft-clamp: the ALiBi forms plus the clamp (slopes or none), under the same rule
+    dim3 kgrid((p.n + TK - 1) / TK, p.b * a.Hkv);
+    if (p.dh == 16 && p.dq_part && p.dq_part_floats >= part_need && attn_fused_bwd_on()) {
+      a.dQp = p.dq_part;
+      hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, true, true, true, true>), kgrid, dim3(256), 0, s, a);
+      const int64_t units = (int64_t)p.b * p.H * p.n * 4;
+      hipLaunchKernelGGL(k_attn_dq_reduce<16>, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, a, p.b * p.H);
+    } else if (p.dh == 16) {
+      hipLaunchKernelGGL((k_attn_bwd_dkdv<16, false, true, true, true, true>), kgrid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((k_attn_bwd_dq<16, true, true, true>), grid, dim3(256), 0, s, a);
+    } else if (p.dh == 32) {
+      hipLaunchKernelGGL((k_attn_bwd_dkdv<32, false, true, true, true, true>), kgrid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((k_attn_bwd_dq<32, true, true, true>), grid, dim3(256), 0, s, a);
+    } else {
+      hipLaunchKernelGGL((k_attn_bwd_dkdv<64, false, true, true, true, true>), kgrid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((k_attn_bwd_dq<64, true, true, true>), grid, dim3(256), 0, s, a);
+    }
+  } else if (p.alibi) {
     // ALiBi: the GQA forms with the bias (a.Hkv = H without grouped-query attention: a group of one query
     // head per kv head), under GQA's rule — no one-launch fused backward, the partial-workspace form when
     // the caller gave the workspace, else the kernel pair
@@ -1247,11 +1328,11 @@ AttnProblem contiguous_problem(const int32_t* lens, int b, int H, int n, int dh,
 
 }  // namespace xtrl
 
-extern "C" int xtrl_attn_fwd_alibi(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
-                                   float* lse, const float* mem_k, const float* mem_v, int b, int H, int Hkv, int n,
-                                   int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
-                                   int window, int num_mem_kv, int add_zero_kv, const float* alibi_slopes,
-                                   void* stream) {
+extern "C" int xtrl_attn_fwd_softclamp(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
+                                       float* lse, const float* mem_k, const float* mem_v, int b, int H, int Hkv,
+                                       int n, int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset,
+                                       uint32_t sub, int window, int num_mem_kv, int add_zero_kv,
+                                       const float* alibi_slopes, float softclamp, void* stream) {
   XTRL_REQUIRE(Hkv >= 1, "attn_fwd: kv heads %d < 1", Hkv);
   xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv);
   pr.mem_k = mem_k;
@@ -1259,7 +1340,17 @@ extern "C" int xtrl_attn_fwd_alibi(const float* q, const float* k, const float* 
   pr.mem_kv = num_mem_kv;
   pr.zero_kv = add_zero_kv;
   pr.alibi = alibi_slopes;
+  pr.softclamp = softclamp;
   return xtrl::attn_fwd_ex(pr, q, k, v, o, lse, nullptr, nullptr, xtrl::as_stream(stream));
+}
+
+extern "C" int xtrl_attn_fwd_alibi(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
+                                   float* lse, const float* mem_k, const float* mem_v, int b, int H, int Hkv, int n,
+                                   int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
+                                   int window, int num_mem_kv, int add_zero_kv, const float* alibi_slopes,
+                                   void* stream) {
+  return xtrl_attn_fwd_softclamp(q, k, v, lens, o, lse, mem_k, mem_v, b, H, Hkv, n, dh, scale, dropout_p, seed, offset,
+                                 sub, window, num_mem_kv, add_zero_kv, alibi_slopes, 0.f, stream);
 }
 
 extern "C" int xtrl_attn_fwd_sink(const float* q, const float* k, const float* v, const int32_t* lens, float* o,
@@ -1297,14 +1388,14 @@ extern "C" int64_t xtrl_attn_sink_ws_floats(int b, int H, int num_mem_kv, int dh
   return xtrl::attn_sink_ws_floats(b, H, num_mem_kv, dh);
 }
 
-extern "C" int xtrl_attn_bwd_part_alibi(const float* q, const float* k, const float* v, const int32_t* lens,
-                                        const float* o, const float* lse, const float* dout, float* dq, float* dk,
-                                        float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats,
-                                        const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v,
-                                        float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh,
-                                        float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
-                                        int window, int num_mem_kv, int add_zero_kv, const float* alibi_slopes,
-                                        void* stream) {
+extern "C" int xtrl_attn_bwd_part_softclamp(const float* q, const float* k, const float* v, const int32_t* lens,
+                                            const float* o, const float* lse, const float* dout, float* dq, float* dk,
+                                            float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats,
+                                            const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v,
+                                            float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv, int n,
+                                            int dh, float scale, float dropout_p, uint64_t seed, uint32_t offset,
+                                            uint32_t sub, int window, int num_mem_kv, int add_zero_kv,
+                                            const float* alibi_slopes, float softclamp, void* stream) {
   XTRL_REQUIRE(Hkv >= 1, "attn_bwd: kv heads %d < 1", Hkv);
   xtrl::AttnProblem pr = xtrl::contiguous_problem(lens, b, H, n, dh, scale, dropout_p, seed, offset, sub, window, Hkv);
   pr.dq_part = dq_part;
@@ -1318,7 +1409,34 @@ extern "C" int xtrl_attn_bwd_part_alibi(const float* q, const float* k, const fl
   pr.sink_ws = sink_ws;
   pr.sink_ws_floats = sink_ws_floats;
   pr.alibi = alibi_slopes;
+  pr.softclamp = softclamp;
   return xtrl::attn_bwd_ex(pr, q, k, v, o, lse, dout, dq, dk, dv, delta_ws, xtrl::as_stream(stream));
+}
+
+extern "C" int xtrl_attn_bwd_softclamp(const float* q, const float* k, const float* v, const int32_t* lens,
+                                       const float* o, const float* lse, const float* dout, float* dq, float* dk,
+                                       float* dv, float* delta_ws, const float* mem_k, const float* mem_v,
+                                       float* dmem_k, float* dmem_v, float* sink_ws, int64_t sink_ws_floats, int b,
+                                       int H, int Hkv, int n, int dh, float scale, float dropout_p, uint64_t seed,
+                                       uint32_t offset, uint32_t sub, int window, int num_mem_kv, int add_zero_kv,
+                                       const float* alibi_slopes, float softclamp, void* stream) {
+  return xtrl_attn_bwd_part_softclamp(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, nullptr, 0, mem_k, mem_v,
+                                      dmem_k, dmem_v, sink_ws, sink_ws_floats, b, H, Hkv, n, dh, scale, dropout_p, seed,
+                                      offset, sub, window, num_mem_kv, add_zero_kv, alibi_slopes, softclamp, stream);
+}
+
+extern "C" int xtrl_attn_bwd_part_alibi(const float* q, const float* k, const float* v, const int32_t* lens,
+                                        const float* o, const float* lse, const float* dout, float* dq, float* dk,
+                                        float* dv, float* delta_ws, float* dq_part, int64_t dq_part_floats,
+                                        const float* mem_k, const float* mem_v, float* dmem_k, float* dmem_v,
+                                        float* sink_ws, int64_t sink_ws_floats, int b, int H, int Hkv, int n, int dh,
+                                        float scale, float dropout_p, uint64_t seed, uint32_t offset, uint32_t sub,
+                                        int window, int num_mem_kv, int add_zero_kv, const float* alibi_slopes,
+                                        void* stream) {
+  return xtrl_attn_bwd_part_softclamp(q, k, v, lens, o, lse, dout, dq, dk, dv, delta_ws, dq_part, dq_part_floats, mem_k,
+                                      mem_v, dmem_k, dmem_v, sink_ws, sink_ws_floats, b, H, Hkv, n, dh, scale,
+                                      dropout_p, seed, offset, sub, window, num_mem_kv, add_zero_kv, alibi_slopes, 0.f,
+                                      stream);
 }
 
 extern "C" int xtrl_attn_bwd_alibi(const float* q, const float* k, const float* v, const int32_t* lens, const float* o,

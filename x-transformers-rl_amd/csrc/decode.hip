@@ -369,7 +369,10 @@ __device__ __forceinline__ float sink_fold(float ts, int zero_kv, float& mx, flo
 // factor 1, terms 0): the cached key at window-relative position j takes - slope[h] (tw - j), its distance
 // to the query at tw measured after the window's pointer shift by j_lo ((t - j_lo) - (j_abs - j_lo) = t -
 // j_abs); the new key (j = tw) and the sinks take none
-template <int DH, int FJ, bool SINK = false, bool ALIBI = false>
+// Logit soft-clamp (CAP = true, D.attn_softclamp = c > 0; always on the ALiBi forms, whose slope is 0 when
+// D.alibi_slopes is NULL): every score of the step — the cached keys' after their ALiBi term, the new key's
+// and the memory rows' — becomes c tanh(score / c); the zero key's 0 stays 0
+template <int DH, int FJ, bool SINK = false, bool ALIBI = false, bool CAP = false>
 __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDecodeDesc D, const XtrlDecodeLayer Ly, int layer,
                                                       int t, const FrPost fp) {
   constexpr int CK = DH <= 32 ? 128 : 64;          // keys per chunk
@@ -486,7 +489,11 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
   for (int i = 0; i < DH; ++i) qreg[i] = qs[i];
   float ts = -INFINITY;   // SINK: memory row `lane`'s score
   if constexpr (SINK) ts = sink_score<DH>(Ly.mem_k, kvh, D.num_mem_kv, lane, qreg, scale);
-  const float slope = ALIBI ? D.alibi_slopes[h] : 0.f;
+  const float slope = ALIBI ? ((CAP && !D.alibi_slopes) ? 0.f : D.alibi_slopes[h]) : 0.f;
+  const float cap = D.attn_softclamp, inv_cap = CAP ? 1.f / D.attn_softclamp : 0.f;
+  if constexpr (CAP) {
+    if (lane < D.num_mem_kv) ts = cap * tanhf(ts * inv_cap);   // (the other lanes keep -inf)
+  }
   // scores, one key per lane; chunk 0 from the prefetched rows
   float mx = -INFINITY;
   for (int j0 = 0; j0 <= tw; j0 += CK) {
@@ -521,6 +528,7 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
       }
       s *= scale;
       if constexpr (ALIBI) s -= slope * (float)(tw - j);   // (j = tw, the new key: 0)
+      if constexpr (CAP) s = cap * tanhf(s * inv_cap);
       if (j <= tw) {
         sc[j] = s;
         mx = fmaxf(mx, s);
@@ -1444,7 +1452,9 @@ int launch_attn_decode(const XtrlDecodeDesc* D, int l, int t, hipStream_t s, con
   if (attn_fused(D, l)) {   // one workgroup of H waves per live row
     const size_t lds = ((size_t)D->H * (D->Tmax + 3 * D->dh) + (size_t)D->H * D->d) * sizeof(float);
     const dim3 grid(D->E), blk(64 * D->H);
-    if (D->alibi_slopes && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    if (D->attn_softclamp > 0.f && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    else if (D->attn_softclamp > 0.f) hipLaunchKernelGGL((k_attn_decode<16, 1, true, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    else if (D->alibi_slopes && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
     else if (D->alibi_slopes) hipLaunchKernelGGL((k_attn_decode<16, 1, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
     else if (sinks && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
     else if (sinks) hipLaunchKernelGGL((k_attn_decode<16, 1, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
@@ -1457,7 +1467,11 @@ int launch_attn_decode(const XtrlDecodeDesc* D, int l, int t, hipStream_t s, con
   const size_t lds = 4 * (size_t)(D->Tmax + 3 * D->dh) * sizeof(float);
   XTRL_REQUIRE(lds <= 160 * 1024, "attn_decode: Tmax %d too large for LDS", D->Tmax);
   dim3 grid((waves + 3) / 4);
-  if (D->alibi_slopes) {   // the ALiBi forms (on the SINK ones, with or without sinks)
+  if (D->attn_softclamp > 0.f) {   // the soft-clamp forms (on the ALiBi ones, with or without slopes)
+    if (D->dh == 16) hipLaunchKernelGGL((k_attn_decode<16, 0, true, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
+    else if (D->dh == 32) hipLaunchKernelGGL((k_attn_decode<32, 0, true, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
+    else hipLaunchKernelGGL((k_attn_decode<64, 0, true, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
+  } else if (D->alibi_slopes) {   // the ALiBi forms (on the SINK ones, with or without sinks)
     if (D->dh == 16) hipLaunchKernelGGL((k_attn_decode<16, 0, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
     else if (D->dh == 32) hipLaunchKernelGGL((k_attn_decode<32, 0, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
     else hipLaunchKernelGGL((k_attn_decode<64, 0, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
@@ -1910,8 +1924,9 @@ constexpr uint32_t HG_CANCEL = 0xFFFFFFFFu;
 // takes 4 d / Ge of the heads' hidden units and its partial of the last Linear; the partials meet
 // through k_mlp's hand-off (sc1 stores, one counter per row) and the last arriver sums them in
 // workgroup order, adds b2 and samples.  The heads are ~40 % of a row's weight bytes (C2).
-// SINK: attention sinks, as k_attn_decode<., ., true>; ALIBI (always with SINK): as k_attn_decode<., ., true, true>
-template <int DH, int KP = (DH == 16 ? 2 : 1), bool SINK = false, bool ALIBI = false>   // KP: 64-key K passes per round trip
+// SINK: attention sinks, as k_attn_decode<., ., true>; ALIBI (always with SINK): as k_attn_decode<., ., true, true>;
+// CAP (always with ALIBI): the logit soft-clamp, as k_attn_decode<., ., true, true, true>
+template <int DH, int KP = (DH == 16 ? 2 : 1), bool SINK = false, bool ALIBI = false, bool CAP = false>   // KP: 64-key K passes per round trip
 __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, int t, int G, const HostGate hg) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ int rows_sh[EMB_MAX_E];
@@ -2115,6 +2130,8 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
           for (int i = 0; i < DH; ++i) kn += __shfl(q, i, 64) * __shfl(k, i, 64);
         }
         kn *= scale;   // the new key's score, k_attn_decode's channel order
+        const float cap = D.attn_softclamp, inv_cap = CAP ? 1.f / D.attn_softclamp : 0.f;
+        if constexpr (CAP) kn = cap * tanhf(kn * inv_cap);
         wave_sync();
         const float4* q4 = reinterpret_cast<const float4*>(att + h * DH);
         // scores of the cached keys, one key per lane, NP 64-key passes in flight
@@ -2128,7 +2145,7 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
         const float* kcw = Ly.k_cache + cb + (int64_t)j_lo * DH;
         const float* vcw = Ly.v_cache + cb + (int64_t)j_lo * DH;
         float* scw = sc + j_lo;
-        const float slope = ALIBI ? D.alibi_slopes[h] : 0.f;   // (the new key's score kn takes no bias)
+        const float slope = ALIBI ? ((CAP && !D.alibi_slopes) ? 0.f : D.alibi_slopes[h]) : 0.f;   // (the new key's score kn takes no bias)
         float mx = kn;
         for (int j0 = 0; j0 < tw; j0 += 64 * NP) {
           float4 kr[NP][F4];
@@ -2152,6 +2169,7 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
             }
             s_ *= scale;
             if constexpr (ALIBI) s_ -= slope * (float)(tw - j);   // the distance after the shift by j_lo
+            if constexpr (CAP) s_ = cap * tanhf(s_ * inv_cap);
             if (j < tw) {
               scw[j] = s_;
               mx = fmaxf(mx, s_);
@@ -2196,7 +2214,10 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
         float fs = 1.f;
         float4 sk4 = make_float4(0.f, 0.f, 0.f, 0.f);   // SINK: the memory rows' P.V, the factor of the other terms
         if constexpr (SINK) {
-          const float ts = sink_score<DH>(Ly.mem_k, kvh, D.num_mem_kv, lane, att + h * DH, scale);
+          float ts = sink_score<DH>(Ly.mem_k, kvh, D.num_mem_kv, lane, att + h * DH, scale);
+          if constexpr (CAP) {
+            if (lane < D.num_mem_kv) ts = cap * tanhf(ts * inv_cap);   // (the other lanes keep -inf)
+          }
           float ps;
           fs = sink_fold(ts, D.add_zero_kv, mx, sum, ps);
           for (int m = 0; m < D.num_mem_kv; ++m) {
@@ -2376,7 +2397,11 @@ int decode_step_rows(const XtrlDecodeDesc* D, int t, int max_rows, hipStream_t s
   const size_t lds = (size_t)row_lds(*D).tot * sizeof(float);
   if (hg.go) XTRL_REQUIRE(grid.x == 1 && D->act_host, "decode rows: the gated host step takes one row (E == 1) "
                                                        "and the pinned action buffer");
-  if (D->alibi_slopes) {   // the ALiBi forms (on the SINK ones, with or without sinks)
+  if (D->attn_softclamp > 0.f) {   // the soft-clamp forms (on the ALiBi ones, with or without slopes)
+    if (D->dh == 16) hipLaunchKernelGGL((k_decode_row<16, 2, true, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+    else if (D->dh == 32) hipLaunchKernelGGL((k_decode_row<32, 1, true, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+    else hipLaunchKernelGGL((k_decode_row<64, 1, true, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+  } else if (D->alibi_slopes) {   // the ALiBi forms (on the SINK ones, with or without sinks)
     if (D->dh == 16) hipLaunchKernelGGL((k_decode_row<16, 2, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
     else if (D->dh == 32) hipLaunchKernelGGL((k_decode_row<32, 1, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
     else hipLaunchKernelGGL((k_decode_row<64, 1, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);

@@ -259,6 +259,11 @@ struct AttnProblem {
   // scale q_i . k_j - alibi[h] (i - j), added before the masks; the sinks take no bias.  No parameter, no
   // gradient.  NULL: none (today's kernels); set: the general forms (run-time kv head mapping and window)
   const float* alibi = nullptr;
+  // logit soft-clamp (x-transformers attn_softclamp_logits / attn_logit_softclamp_value): c > 0 turns the
+  // score x of a real key (ALiBi term included) and of a memory column into c tanh(x / c), before the masks;
+  // the zero key's 0 stays 0.  The backward multiplies dS by 1 - tanh^2(x / c).  No parameter.  0: off
+  // (today's kernels); set: the general forms, as for alibi
+  float softclamp = 0.f;
 };
 constexpr int kMaxMemKV = 16;   // one 16-column MFMA sub-tile
 inline bool attn_has_sinks(const AttnProblem& p) { return p.mem_kv > 0 || p.zero_kv != 0; }

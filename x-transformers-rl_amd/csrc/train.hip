@@ -1252,6 +1252,7 @@ AttnProblem attn_problem(const Ctx& c, const XtrlTrainLayer& Ly, int li) {
   p.dq_part_floats = D->dq_part_floats;
   p.window = D->attn_window;
   p.alibi = D->alibi_slopes;   // ALiBi: slopes [H], the same for every layer (NULL: none)
+  p.softclamp = D->attn_softclamp;   // logit soft-clamp value (0: off)
   // grouped-query attention: k, v (and dk, dv) are token rows of the same buffers as q (dq), Hkv heads wide
   p.Hkv = kv_heads(D);
   p.kv = p.in;

@@ -13,7 +13,7 @@ from pathlib import Path
 import torch   # noqa: F401  (load torch's HIP runtime first so the library binds to the same one)
 
 LIB_PATH = Path(os.environ.get('XTRL_LIB', Path(__file__).resolve().parent / 'libxtrl_hip.so'))   # override: A/B experiments
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 P = C.c_void_p
 I32, I64, U32, U64, F32 = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
@@ -56,7 +56,7 @@ class DecodeDesc(C.Structure):
                 + [(n, P) for n in ('w_h1x', 'heads_part', 'heads_cnt', 'row_part', 'row_cnt')]
                 + [('ff_glu', I32), ('hglu', P), ('qk_norm', I32), ('attn_scale', F32), ('xpos_base', F32),
                    ('rms_norm', I32), ('act_host', P), ('attn_window', I32), ('Hkv', I32),
-                   ('alibi_slopes', P), ('num_mem_kv', I32), ('add_zero_kv', I32)])
+                   ('alibi_slopes', P), ('attn_softclamp', F32), ('num_mem_kv', I32), ('add_zero_kv', I32)])
 
 
 class FractalLevel(C.Structure):
@@ -135,7 +135,7 @@ class TrainDesc(C.Structure):
                    ('Hkv', I32), ('wimg', P), ('wimg_bytes', I64), ('wimg_tab', P),
                    ('wimg_tab_host', C.POINTER(WimgEntry)), ('wimg_n', I32), ('alibi_slopes', P),
                    ('wfrag', P), ('wfrag_bytes', I64), ('wfrag_tab', P), ('wfrag_tab_host', C.POINTER(WfragEntry)),
-                   ('wfrag_n', I32),
+                   ('wfrag_n', I32), ('attn_softclamp', F32),
                    ('num_mem_kv', I32), ('add_zero_kv', I32), ('sink_ws', P), ('sink_ws_floats', I64)])
 
 
@@ -220,6 +220,12 @@ SIGNATURES = {
                                   U64, U32, U32, I32, I32, I32, P, P]),
     'xtrl_attn_bwd_part_alibi': (I32, [P, P, P, P, P, P, P, P, P, P, P, P, I64, P, P, P, P, P, I64, I32, I32, I32, I32,
                                        I32, F32, F32, U64, U32, U32, I32, I32, I32, P, P]),
+    'xtrl_attn_fwd_softclamp': (I32, [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, F32, U64, U32, U32, I32, I32,
+                                      I32, P, F32, P]),
+    'xtrl_attn_bwd_softclamp': (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I32, I32, I32, I32, I32, F32,
+                                      F32, U64, U32, U32, I32, I32, I32, P, F32, P]),
+    'xtrl_attn_bwd_part_softclamp': (I32, [P, P, P, P, P, P, P, P, P, P, P, P, I64, P, P, P, P, P, I64, I32, I32, I32,
+                                           I32, I32, F32, F32, U64, U32, U32, I32, I32, I32, P, F32, P]),
     'xtrl_loss_fwd': (I32, [C.POINTER(LossDesc), P]),
     'xtrl_loss_bwd': (I32, [C.POINTER(LossDesc), F32, P]),
     'xtrl_grad_norm': (I32, [P, I64, P, F32, P, P]),

@@ -60,7 +60,8 @@ XT_DEFAULTS = dict(
     attn_talking_heads=False, attn_head_scale=False, attn_sparse_topk=None, attn_num_mem_kv=0, attn_on_attn=False,
     attn_gate_value_heads=False, attn_swiglu_values=False, attn_qk_norm=False, attn_one_kv_head=False,
     attn_kv_heads=None, attn_shared_kv=False, attn_value_dim_head=None, attn_add_zero_kv=False,
-    attn_rotary_embed_values=False, attn_max_attend_past=None, alibi_num_heads=None, alibi_learned=False)
+    attn_rotary_embed_values=False, attn_max_attend_past=None, alibi_num_heads=None, alibi_learned=False,
+    attn_softclamp_logits=False, attn_logit_softclamp_value=50.)
 
 
 MAX_MEM_KV = 16   # attn_num_mem_kv: the memory rows are one 16-column MFMA sub-tile (kernels.h kMaxMemKV)
@@ -130,7 +131,7 @@ class Agent(nn.Module):
                  'learned_value_residual_mix', 'ff_mult', 'ff_no_bias', 'ff_glu', 'attn_qk_norm',
                  'attn_qk_norm_scale', 'rotary_xpos', 'rotary_xpos_scale_base', 'use_rmsnorm',
                  'attn_max_attend_past', 'attn_one_kv_head', 'attn_num_mem_kv', 'attn_add_zero_kv',
-                 'alibi_pos_bias', 'alibi_num_heads'}
+                 'alibi_pos_bias', 'alibi_num_heads', 'attn_softclamp_logits', 'attn_logit_softclamp_value'}
         if 'alibi_learned' in wm:   # (not at its default: those were dropped above)
             raise NotImplementedError('alibi_learned is not supported by the MI355X decoder: the ALiBi slopes are the '
                                       'fixed geometric sequence (alibi_pos_bias), without parameters')
@@ -190,6 +191,20 @@ class Agent(nn.Module):
                 raise ValueError(f'alibi_num_heads must be an int from 1 to heads = {heads}, or None (every head), '
                                  f'not {alibi_heads!r}')
         alibi_heads = (int(alibi_heads) if alibi_heads is not None else int(heads)) if alibi else 0
+        # logit soft-clamp (x-transformers attn_softclamp_logits / attn_logit_softclamp_value, Gemma 2): the scores
+        # become c tanh(score / c) after the ALiBi bias and before the masks; no parameters
+        softclamp_on = wm.get('attn_softclamp_logits', False)
+        if not isinstance(softclamp_on, (bool, np.bool_)):
+            raise ValueError(f'attn_softclamp_logits must be a bool, not {softclamp_on!r}')
+        softclamp = XT_DEFAULTS['attn_logit_softclamp_value']
+        if 'attn_logit_softclamp_value' in wm:   # (not at its default: those were dropped above)
+            softclamp = wm['attn_logit_softclamp_value']
+            if isinstance(softclamp, (bool, np.bool_)) or not isinstance(softclamp, (int, float, np.integer, np.floating)) \
+                    or not math.isfinite(softclamp) or not softclamp > 0:
+                raise ValueError(f'attn_logit_softclamp_value must be a finite number > 0, not {softclamp!r}')
+            if not softclamp_on:
+                raise ValueError(f'attn_logit_softclamp_value={softclamp!r} needs attn_softclamp_logits=True')
+        softclamp = float(softclamp) if softclamp_on else 0.
         self.seed = int(seed)
         self.evolutionary = evolutionary
         self.evolve_every, self.evolve_after_step = evolve_every, evolve_after_step
@@ -209,6 +224,7 @@ class Agent(nn.Module):
                         xpos_scale_base=float(wm.get('rotary_xpos_scale_base', 512.)),
                         rotary_abs_rollout=rotary_abs_rollout, attn_window=int(window or 0), kv_heads=kv_heads,
                         num_mem_kv=int(num_mem_kv), add_zero_kv=bool(add_zero_kv), alibi_heads=alibi_heads,
+                        softclamp=softclamp,
                         hl_reduction_mean=hl_reduction_mean, hl_sigma_ratio=hl_sigma_ratio)
         self.cfg = c
         # the learn step without the minibatch's padding (XtrlTrainDesc.packed): exact only with the
@@ -231,6 +247,9 @@ class Agent(nn.Module):
                                           'and attn_add_zero_kv at False')
             if c.alibi_heads:
                 raise NotImplementedError('the fractal policy body has no ALiBi: leave alibi_pos_bias at False')
+            if c.softclamp:
+                raise NotImplementedError('the fractal policy body has no logit soft-clamp: leave attn_softclamp_logits '
+                                          'at False')
             if c.gate_values or c.value_residual or c.ff_no_bias or c.ff_glu or c.qk_norm or c.rotary_xpos or c.rms_norm:
                 raise NotImplementedError('the fractal policy body has no gated values / value residual / bias-free or '
                                           'GLU feed-forward / qk norm / xPos rotary / RMSNorm: set attn_gate_values / '

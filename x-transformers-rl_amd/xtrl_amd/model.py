@@ -57,6 +57,7 @@ class ModelConfig:
     num_mem_kv: int = 0                  # x-transformers attn_num_mem_kv: learned memory key / value rows per kv head
     add_zero_kv: bool = False            # x-transformers attn_add_zero_kv: one all-zero key / value ("+ 1" softmax)
     alibi_heads: int = 0                 # x-transformers alibi_pos_bias: heads with an ALiBi slope (alibi_num_heads); 0: off
+    softclamp: float = 0.                # x-transformers attn_softclamp_logits: attn_logit_softclamp_value; 0: off
     rotary_abs_rollout: bool = False     # decision log: reference semantics = rotary position 0 in rollout
     hl_reduction_mean: bool = True       # decision log: hl-gauss-pytorch default reduction
     hl_sigma_ratio: float = 2.0
@@ -382,7 +383,7 @@ class WorldModelActorCritic(nn.Module):
             k = torch.cat((k[..., :rot] * cos * xk + _rotate_half(k[..., :rot]) * sin * xk, k[..., rot:]), dim=-1)
             o = ops.attention(q, k, v, lens, scale, p_drop, attn_seed, attn_offset, li, window=c.attn_window,
                               mem_k=getattr(blk, 'mem_k', None), mem_v=getattr(blk, 'mem_v', None),
-                              add_zero_kv=c.add_zero_kv, alibi_slopes=self.alibi_slopes)
+                              add_zero_kv=c.add_zero_kv, alibi_slopes=self.alibi_slopes, softclamp=c.softclamp)
             o = o.permute(0, 2, 1, 3).reshape(b, n, I)
             if gate_pre is not None:
                 o = o * gate_pre.sigmoid()

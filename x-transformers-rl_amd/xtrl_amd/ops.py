@@ -223,11 +223,14 @@ class AttentionFn(torch.autograd.Function):
     Attention sinks: mem_k, mem_v [Hkv][M][dh] (or None) and add_zero_kv join every row's softmax
     (include/xtrl_hip.h, xtrl_attn_fwd_sink); their gradients come back with dq, dk, dv.
     ALiBi: alibi_slopes [H] fp32 (or None) subtracts slope[h] (i - j) from the real keys' scores
-    (xtrl_attn_fwd_alibi; no gradient).  Without slopes the calls are the _sink ones."""
+    (xtrl_attn_fwd_alibi; no gradient).  Without slopes the calls are the _sink ones.
+    Logit soft-clamp: softclamp = c > 0 turns the real keys' and the memory columns' scores x (ALiBi term
+    included) into c tanh(x / c) before the masks (xtrl_attn_fwd_softclamp / xtrl_attn_bwd_softclamp, with
+    or without slopes); 0: off, the calls above."""
 
     @staticmethod
     def forward(ctx, q, k, v, lens, scale, dropout_p, seed, offset, sub, window=0, mem_k=None, mem_v=None,
-                add_zero_kv=False, alibi_slopes=None):
+                add_zero_kv=False, alibi_slopes=None, softclamp=0.):
         lib = L.lib()
         b, H, n, dh = q.shape
         Hkv = k.shape[1]
@@ -250,12 +253,17 @@ class AttentionFn(torch.autograd.Function):
         args = (L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(mem_k) if M else None,
                 L.ptr(mem_v) if M else None, b, H, Hkv, n, dh, float(scale), float(dropout_p), int(seed), int(offset),
                 int(sub), int(window), M, int(bool(add_zero_kv)))
-        if alibi_slopes is not None:
+        softclamp = float(softclamp)
+        if softclamp != 0.:   # (a negative or non-finite value is the library's to refuse)
+            L.check(lib.xtrl_attn_fwd_softclamp(*args, L.ptr(alibi_slopes) if alibi_slopes is not None else None,
+                                                softclamp, L.stream()), 'attn_fwd')
+        elif alibi_slopes is not None:
             L.check(lib.xtrl_attn_fwd_alibi(*args, L.ptr(alibi_slopes), L.stream()), 'attn_fwd')
         else:
             L.check(lib.xtrl_attn_fwd_sink(*args, L.stream()), 'attn_fwd')
         ctx.save_for_backward(q, k, v, lens, o, lse, *((mem_k, mem_v) if M else ()))
         ctx.alibi = alibi_slopes   # (no gradient: not a saved tensor of the graph)
+        ctx.softclamp = softclamp
         ctx.cfg = (float(scale), float(dropout_p), int(seed), int(offset), int(sub), int(window), M,
                    int(bool(add_zero_kv)))
         return o
@@ -280,11 +288,14 @@ class AttentionFn(torch.autograd.Function):
         args = (L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do), L.ptr(dq), L.ptr(dk),
                 L.ptr(dv), L.ptr(delta), pm(mem_k), pm(mem_v), pm(dmk), pm(dmv), pm(ws), ws_floats, b, H, k.shape[1],
                 n, dh, scale, p, seed, offset, sub, window, M, Z)
-        if ctx.alibi is not None:
+        if ctx.softclamp != 0.:
+            L.check(lib.xtrl_attn_bwd_softclamp(*args, L.ptr(ctx.alibi) if ctx.alibi is not None else None,
+                                                ctx.softclamp, L.stream()), 'attn_bwd')
+        elif ctx.alibi is not None:
             L.check(lib.xtrl_attn_bwd_alibi(*args, L.ptr(ctx.alibi), L.stream()), 'attn_bwd')
         else:
             L.check(lib.xtrl_attn_bwd_sink(*args, L.stream()), 'attn_bwd')
-        return dq, dk, dv, None, None, None, None, None, None, None, dmk, dmv, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None, dmk, dmv, None, None, None
 
 
 def alibi_slopes(heads, alibi_heads=None):
@@ -304,19 +315,21 @@ def alibi_slopes(heads, alibi_heads=None):
 
 
 def attention(q, k, v, lens, scale, dropout_p=0., seed=0, offset=0, sub=0, window=0, mem_k=None, mem_v=None,
-              add_zero_kv=False, alibi_slopes=None):
+              add_zero_kv=False, alibi_slopes=None, softclamp=0.):
     """``offset`` / ``sub``: the dropout stream (Philox c2 base and c3 sub-index = decoder layer);
     ``window`` > 0: query i sees key j only if i - j <= window (x-transformers max_attend_past).
     k, v with fewer heads than q (a divisor): grouped-query attention (x-transformers attn_kv_heads).
     ``mem_k`` / ``mem_v`` [Hkv][M][dh] and ``add_zero_kv``: attention sinks every row sees (x-transformers
     attn_num_mem_kv / attn_add_zero_kv).  ``alibi_slopes`` [H] fp32: the ALiBi distance penalty
-    - slope[h] (i - j) on the real keys' scores (x-transformers alibi_pos_bias; `alibi_slopes()` above)."""
+    - slope[h] (i - j) on the real keys' scores (x-transformers alibi_pos_bias; `alibi_slopes()` above).
+    ``softclamp`` = c > 0: the scores of the real keys (after the ALiBi term) and of the memory columns become
+    c tanh(score / c) before the masks (x-transformers attn_softclamp_logits / attn_logit_softclamp_value)."""
     if mem_k is not None:
         mem_k, mem_v = mem_k.contiguous(), mem_v.contiguous()
     if alibi_slopes is not None:
         alibi_slopes = alibi_slopes.detach().contiguous()
     return AttentionFn.apply(q.contiguous(), k.contiguous(), v.contiguous(), lens, scale, dropout_p, seed, offset,
-                             sub, window, mem_k, mem_v, add_zero_kv, alibi_slopes)
+                             sub, window, mem_k, mem_v, add_zero_kv, alibi_slopes, softclamp)
 
 
 # --------------------------------------------------------------------------------------------

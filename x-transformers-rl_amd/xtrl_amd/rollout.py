@@ -184,6 +184,7 @@ class RolloutEngine:
         if int(getattr(c, 'alibi_heads', 0)):
             self.alibi_slopes = ops.alibi_slopes(c.heads, c.alibi_heads).to(self.dev)
             D.alibi_slopes = self.alibi_slopes.data_ptr()
+        D.attn_softclamp = float(getattr(c, 'softclamp', 0.))   # logit soft-clamp value (0: off)
         D.sim_mode, D.hazard_log2, D.rs_eps = self.sim_mode, hazard_log2, 1e-5
         if clamp is not None:
             D.clamp_lo, D.clamp_hi, D.has_clamp = float(clamp[0]), float(clamp[1]), 1
@@ -699,6 +700,7 @@ class FractalRolloutEngine(RolloutEngine):
         self.desc.Hkv = 0           # (nor grouped-query attention)
         self.desc.num_mem_kv = self.desc.add_zero_kv = 0   # (nor attention sinks)
         self.desc.alibi_slopes = None   # (nor ALiBi)
+        self.desc.attn_softclamp = 0.   # (nor the logit soft-clamp)
         Lv = self.levels
         levels = (L.FractalLevel * Lv)()
         names = [n for n, _ in L.FractalLevel._fields_]

@@ -215,6 +215,7 @@ class FusedTrainStep:
             from . import ops
             self.alibi_slopes = ops.alibi_slopes(H, c.alibi_heads).to(dev)
             D.alibi_slopes = self.alibi_slopes.data_ptr()
+        D.attn_softclamp = float(getattr(c, 'softclamp', 0.))   # logit soft-clamp value (0: off)
         D.inv_freq = self.inv_freq.data_ptr()
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
@@ -446,6 +447,7 @@ class FractalTrainStep(FusedTrainStep):
         D.Hkv = 0           # (nor grouped-query attention)
         D.num_mem_kv = D.add_zero_kv = 0   # (nor attention sinks)
         D.alibi_slopes = None              # (nor ALiBi)
+        D.attn_softclamp = 0.              # (nor the logit soft-clamp)
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
         D.part_floats = self.buf['part'].numel()
