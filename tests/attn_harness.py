@@ -1,8 +1,9 @@
 """What the attention GPU tests share (test_gpu_parity.py, test_attn_window_gpu.py, test_attn_gqa_gpu.py,
-test_attn_sink_gpu.py): the one driver of the learn-step attention kernels through the C ABI (attn_lib, which
-reaches every entry-point family: xtrl_attn_fwd / _bwd / _bwd_part and their _win, _gqa and _sink forms), the
-kernel-level problem builder, the fp64 band softmax, the bounds against an fp64 reference (check_ref) and the
-model-level body "rollout, then n learn minibatches against a patched oracle" (rollout_and_learn).  The Learner
+test_attn_sink_gpu.py, test_attn_alibi_gpu.py, test_attn_softclamp_gpu.py): the one driver of the learn-step
+attention kernels through the C ABI (attn_lib, which reaches every entry-point family: xtrl_attn_fwd / _bwd /
+_bwd_part and their _win, _gqa, _sink, _alibi and _softclamp forms), the kernel-level problem builder, the fp64
+band softmax, the one fp64 autograd wrapper over the option files' dense references (fp64_ref), the bounds
+against an fp64 reference (check_ref) and the model-level body "rollout, then n learn minibatches against a patched oracle" (rollout_and_learn).  The Learner
 builder and the other model-level bodies are test_gpu_parity's: make_learner, _packed_vs_padded,
 _fused_vs_autograd, deploy_parity.
 
@@ -37,36 +38,47 @@ def fused_bwd(on):
             os.environ['XTRL_ATTN_FUSED_BWD'] = old
 
 
-def attn_lib(q, k, v, lens, do, scale, p, mode, abi, W=None, mem_k=None, mem_v=None, Z=False, seed=3, offset=1, sub=0):
+def attn_lib(q, k, v, lens, do, scale, p, mode, abi, W=None, mem_k=None, mem_v=None, Z=False, seed=3, offset=1, sub=0,
+             slopes=None, c=0.):
     """Forward + backward through the C ABI; every output and workspace holds NaN before the calls, so an
-    element no kernel wrote shows.  Returns o, lse, delta, dq, dk, dv (and dmk, dmv at M > 0).
+    element no kernel wrote shows.  Returns o, lse, delta, dq, dk, dv (and dmk, dmv at M > 0).  The calls are
+    synchronised and the result dict is left in ``attn_lib.last`` also when one of them raises, so a test of a
+    refused argument can see that no kernel ran.
 
     ``abi``: the entry-point family — 'plain' (xtrl_attn_fwd / xtrl_attn_bwd / xtrl_attn_bwd_part; no window),
     'win' (their _win forms; ``W`` None: the plain ones), 'gqa' (_gqa: k, v [b][Hkv][n][dh]; ``W`` None: window
-    0, none) or 'sink' (_sink: GQA and window as 'gqa', plus mem_k, mem_v [Hkv][M][dh] — None: M = 0, null
-    pointers — and the zero key ``Z``).
+    0, none), 'sink' (_sink: GQA and window as 'gqa', plus mem_k, mem_v [Hkv][M][dh] — None: M = 0, null
+    pointers — and the zero key ``Z``), 'alibi' (_alibi: as 'sink', plus ``slopes`` [H] fp32 on the device, or
+    None: a NULL pointer) or 'softclamp' (_softclamp: as 'alibi', plus the float ``c`` after the slopes; 0: off).
     ``mode``: 'two' (XTRL_ATTN_FUSED_BWD=0: the dK/dV + dQ kernel pair), 'fused' (=1 without a workspace: one
-    launch for n <= 128 at Hkv = H; Hkv < H has no fused form and runs the pair) or 'part' (=1 through
-    xtrl_attn_bwd_part*: the long-episode backward with the dQ partial workspace)."""
+    launch for n <= 128 at Hkv = H without ALiBi or soft-clamp; the other forms have no fused one and run the
+    pair) or 'part' (=1 through xtrl_attn_bwd_part*: the long-episode backward with the dQ partial workspace)."""
     from xtrl_amd import _lib as L
     lib = L.lib()
     b, H, n, dh = q.shape
     Hkv = k.shape[1]
     M = 0 if mem_k is None else mem_k.shape[1]
-    assert abi in ('plain', 'win', 'gqa', 'sink') and mode in ('two', 'fused', 'part'), (abi, mode)
+    FAMILIES = ('plain', 'win', 'gqa', 'sink', 'alibi', 'softclamp')   # each takes what the ones before it take
+    assert abi in FAMILIES and mode in ('two', 'fused', 'part'), (abi, mode)
+    rank = FAMILIES.index(abi)
     assert abi != 'plain' or W is None, f"abi 'plain' takes no window, W = {W}"
-    assert abi in ('gqa', 'sink') or Hkv == H, f'abi {abi!r} takes k, v with all H = {H} heads, not {Hkv}'
-    assert abi == 'sink' or (M == 0 and not Z), f'abi {abi!r} takes no sinks (M = {M}, Z = {Z})'
+    assert rank >= 2 or Hkv == H, f'abi {abi!r} takes k, v with all H = {H} heads, not {Hkv}'
+    assert rank >= 3 or (M == 0 and not Z), f'abi {abi!r} takes no sinks (M = {M}, Z = {Z})'
+    assert rank >= 4 or slopes is None, f'abi {abi!r} takes no slopes'
+    assert slopes is None or (slopes.shape == (H,) and slopes.dtype == torch.float32 and slopes.is_cuda), slopes
+    assert rank >= 5 or c == 0., f'abi {abi!r} takes no soft-clamp value (c = {c})'
     suffix = '' if abi == 'plain' or (abi == 'win' and W is None) else '_' + abi
     nan = lambda *s: torch.full(s, float('nan'), device=DEV)   # noqa: E731
     o, dq, dk, dv = nan(*q.shape), nan(*q.shape), nan(*k.shape), nan(*v.shape)
     lse, delta = nan(b, H, n), nan(b, H, n)
     res = dict(o=o, lse=lse, delta=delta, dq=dq, dk=dk, dv=dv)
-    # the arguments after the pointers: b, H, [Hkv,] n, dh, scale, p, seed, offset, sub, [window,] [M, Z,] stream
-    tail = (b, H) + ((Hkv,) if abi in ('gqa', 'sink') else ()) + (n, dh, scale, p, seed, offset, sub) \
-        + ((int(W or 0),) if suffix else ()) + ((M, int(Z)) if abi == 'sink' else ()) + (L.stream(),)
+    # the arguments after the pointers: b, H, [Hkv,] n, dh, scale, p, seed, offset, sub, [window,] [M, Z,] [slopes,]
+    # [c,] stream
+    tail = (b, H) + ((Hkv,) if rank >= 2 else ()) + (n, dh, scale, p, seed, offset, sub) \
+        + ((int(W or 0),) if suffix else ()) + ((M, int(Z)) if rank >= 3 else ()) \
+        + ((L.ptr(slopes),) if rank >= 4 else ()) + ((float(c),) if rank >= 5 else ()) + (L.stream(),)
     fwd_sink = bwd_sink = ()
-    if abi == 'sink':
+    if rank >= 3:
         nws = int(lib.xtrl_attn_sink_ws_floats(b, H, M, dh))
         dmk, dmv, ws = (nan(Hkv, M, dh), nan(Hkv, M, dh), nan(nws)) if M else (None, None, None)
         fwd_sink = (L.ptr(mem_k), L.ptr(mem_v))
@@ -74,18 +86,53 @@ def attn_lib(q, k, v, lens, do, scale, p, mode, abi, W=None, mem_k=None, mem_v=N
         if M:
             res.update(dmk=dmk, dmv=dmv)
     io = tuple(L.ptr(t) for t in (q, k, v, lens, o, lse))
-    L.check(getattr(lib, 'xtrl_attn_fwd' + suffix)(*io, *fwd_sink, *tail), 'attn_fwd' + suffix)
-    grads = tuple(L.ptr(t) for t in (do, dq, dk, dv, delta))
-    with fused_bwd(mode != 'two'):
-        if mode == 'part':
-            nf = int(lib.xtrl_attn_bwd_part_floats(b, H, n, dh))
-            part = nan(nf)
-            L.check(getattr(lib, 'xtrl_attn_bwd_part' + suffix)(*io, *grads, L.ptr(part), nf, *bwd_sink, *tail),
-                    'attn_bwd_part' + suffix)
-        else:
-            L.check(getattr(lib, 'xtrl_attn_bwd' + suffix)(*io, *grads, *bwd_sink, *tail), 'attn_bwd' + suffix)
-    torch.cuda.synchronize()
+    try:
+        L.check(getattr(lib, 'xtrl_attn_fwd' + suffix)(*io, *fwd_sink, *tail), 'attn_fwd' + suffix)
+        grads = tuple(L.ptr(t) for t in (do, dq, dk, dv, delta))
+        with fused_bwd(mode != 'two'):
+            if mode == 'part':
+                nf = int(lib.xtrl_attn_bwd_part_floats(b, H, n, dh))
+                part = nan(nf)
+                L.check(getattr(lib, 'xtrl_attn_bwd_part' + suffix)(*io, *grads, L.ptr(part), nf, *bwd_sink, *tail),
+                        'attn_bwd_part' + suffix)
+            else:
+                L.check(getattr(lib, 'xtrl_attn_bwd' + suffix)(*io, *grads, *bwd_sink, *tail), 'attn_bwd' + suffix)
+    finally:
+        torch.cuda.synchronize()
+        attn_lib.last = res
     return res
+
+
+def fp64_ref(dense, q, k, v, do, lens, W, extra=(), mem_k=None, mem_v=None, Z=False, keep=None, keep_mem=None):
+    """The fp64 reference of attn_lib's results: ``dense`` — one of the dense references attn_sink_ref,
+    attn_alibi_ref, attn_softclamp_ref of the CPU test modules, called as dense(q, k, v, lens, scale, W, *extra,
+    mem_k, mem_v, Z, keep, keep_mem) — on k, v and the memory rows repeated to the query heads by
+    ops.kv_head_index; autograd sums dk / dv / dmem over each kv head's query heads.  ``extra``: what that
+    reference takes after W — (slopes,) or (slopes, c); a tensor is widened to fp64 (the fp32 slopes), None stays.
+    Without a sink the masked scores take x-transformers' finite fill, so the dead rows of a window (no visible
+    key) are uniform over all n positions; their lse is set to the kernels' convention for such rows, 0.
+    Returns a dict of CPU tensors: o, lse, dq, dk, dv (and dmk, dmv)."""
+    from test_attn_sink_cpu import visible
+    from xtrl_amd import ops
+    H, Hkv, n, dh = q.shape[1], k.shape[1], q.shape[2], q.shape[3]
+    idx = ops.kv_head_index(H, Hkv, device=k.device)
+    leaves = [t.double().requires_grad_() for t in (q, k, v)]
+    mems = [t.double().requires_grad_() for t in (mem_k, mem_v)] if mem_k is not None else [None, None]
+    sinks = mem_k is not None or bool(Z)
+    extra = [x.double().to(q.device) if torch.is_tensor(x) else x for x in extra]
+    fill = {} if sinks else dict(fill=-torch.finfo(torch.float64).max)   # (with sinks: the references' own -inf)
+    o, lse = dense(leaves[0], leaves[1][:, idx], leaves[2][:, idx], lens, dh ** -0.5, W, *extra,
+                   None if mems[0] is None else mems[0][idx], None if mems[1] is None else mems[1][idx], bool(Z),
+                   keep, keep_mem, **fill)
+    (o * do.double()).sum().backward()
+    lse = lse.detach().clone()
+    if not sinks:
+        dead = ~visible(n, lens, W).any(-1)[:, 0]   # [b][n]
+        lse.transpose(1, 2)[dead] = 0.
+    out = dict(o=o, lse=lse, dq=leaves[0].grad, dk=leaves[1].grad, dv=leaves[2].grad)
+    if mems[0] is not None:
+        out.update(dmk=mems[0].grad, dmv=mems[1].grad)
+    return {name: t.detach().cpu() for name, t in out.items()}
 
 
 def ragged_lens(g, b, n):

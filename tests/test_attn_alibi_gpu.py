@@ -15,13 +15,15 @@ from oracle import philox as P
 
 import attn_harness as AH
 import test_gpu_parity as G
-from attn_harness import NAMES, check_ref, fused_bwd, modes_of, problem
+from attn_harness import NAMES, check_ref, modes_of, problem
 from test_attn_alibi_cpu import attn_alibi_ref, install_alibi
-from test_attn_sink_cpu import sink_dropout_keep, visible
+from test_attn_sink_cpu import sink_dropout_keep
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 sink_lib = functools.partial(AH.attn_lib, abi='sink')
+alibi_lib = functools.partial(AH.attn_lib, abi='alibi')   # slopes=None: a NULL slopes pointer
+alibi_ref = functools.partial(AH.fp64_ref, attn_alibi_ref)   # extra = (slopes,)
 SHAPES = [(3, 4, 4, 37, 16, None), (2, 4, 2, 70, 16, None), (2, 4, 2, 130, 16, 10), (2, 4, 1, 200, 16, 64),
           (2, 6, 2, 64, 32, 7), (1, 4, 2, 70, 64, None)]
 SINKS = [(0, 0), (0, 1), (3, 1)]
@@ -32,75 +34,9 @@ SINKS = [(0, 0), (0, 1), (3, 1)]
 # ----------------------------------------------------------------------------------------------
 
 
-def alibi_lib(q, k, v, lens, do, scale, p, mode, slopes, W=None, mem_k=None, mem_v=None, Z=False, seed=3, offset=1,
-              sub=0):
-    """attn_harness.attn_lib's 'sink' family with the slopes: forward + backward through xtrl_attn_fwd_alibi /
-    xtrl_attn_bwd_alibi / xtrl_attn_bwd_part_alibi, every output and workspace NaN before the calls.
-    ``slopes`` [H] fp32 on the device, or None: a NULL pointer.  ``mode`` as attn_lib: 'two' (the kernel pair),
-    'fused' (XTRL_ATTN_FUSED_BWD=1 without a workspace: ALiBi has no one-launch form and runs the pair) or
-    'part' (the partial-workspace form).  Returns o, lse, delta, dq, dk, dv (and dmk, dmv at M > 0)."""
-    from xtrl_amd import _lib as L
-    lib = L.lib()
-    b, H, n, dh = q.shape
-    Hkv = k.shape[1]
-    M = 0 if mem_k is None else mem_k.shape[1]
-    assert mode in ('two', 'fused', 'part'), mode
-    assert slopes is None or (slopes.shape == (H,) and slopes.dtype == torch.float32 and slopes.is_cuda), slopes
-    nan = lambda *s: torch.full(s, float('nan'), device=DEV)   # noqa: E731
-    o, dq, dk, dv = nan(*q.shape), nan(*q.shape), nan(*k.shape), nan(*v.shape)
-    lse, delta = nan(b, H, n), nan(b, H, n)
-    res = dict(o=o, lse=lse, delta=delta, dq=dq, dk=dk, dv=dv)
-    tail = (b, H, Hkv, n, dh, scale, p, seed, offset, sub, int(W or 0), M, int(Z), L.ptr(slopes), L.stream())
-    nws = int(lib.xtrl_attn_sink_ws_floats(b, H, M, dh))
-    dmk, dmv, ws = (nan(Hkv, M, dh), nan(Hkv, M, dh), nan(nws)) if M else (None, None, None)
-    fwd_sink = (L.ptr(mem_k), L.ptr(mem_v))
-    bwd_sink = fwd_sink + (L.ptr(dmk), L.ptr(dmv), L.ptr(ws), nws)
-    if M:
-        res.update(dmk=dmk, dmv=dmv)
-    io = tuple(L.ptr(t) for t in (q, k, v, lens, o, lse))
-    L.check(lib.xtrl_attn_fwd_alibi(*io, *fwd_sink, *tail), 'attn_fwd_alibi')
-    grads = tuple(L.ptr(t) for t in (do, dq, dk, dv, delta))
-    with fused_bwd(mode != 'two'):
-        if mode == 'part':
-            nf = int(lib.xtrl_attn_bwd_part_floats(b, H, n, dh))
-            part = nan(nf)
-            L.check(lib.xtrl_attn_bwd_part_alibi(*io, *grads, L.ptr(part), nf, *bwd_sink, *tail), 'attn_bwd_part_alibi')
-        else:
-            L.check(lib.xtrl_attn_bwd_alibi(*io, *grads, *bwd_sink, *tail), 'attn_bwd_alibi')
-    torch.cuda.synchronize()
-    return res
-
-
 def dev_slopes(H, A=None):
     from xtrl_amd import ops
     return ops.alibi_slopes(H, A).to(DEV)
-
-
-def alibi_ref(q, k, v, do, lens, W, slopes, mem_k=None, mem_v=None, Z=False, keep=None, keep_mem=None):
-    """The fp64 reference (test_attn_alibi_cpu.attn_alibi_ref; the fp32 slopes widened) on k, v and the memory
-    rows repeated to the query heads; autograd sums dk / dv / dmem over each kv head's query heads.  Without a
-    sink the masked scores take x-transformers' finite fill, so the dead rows of a window (no visible key) are
-    uniform over all n positions; their lse is set to the kernels' convention for such rows, 0.
-    Returns a dict of CPU tensors: o, lse, dq, dk, dv (and dmk, dmv)."""
-    from xtrl_amd import ops
-    H, Hkv, n, dh = q.shape[1], k.shape[1], q.shape[2], q.shape[3]
-    idx = ops.kv_head_index(H, Hkv, device=k.device)
-    leaves = [t.double().requires_grad_() for t in (q, k, v)]
-    mems = [t.double().requires_grad_() for t in (mem_k, mem_v)] if mem_k is not None else [None, None]
-    sinks = mem_k is not None or bool(Z)
-    fill = float('-inf') if sinks else -torch.finfo(torch.float64).max
-    o, lse = attn_alibi_ref(leaves[0], leaves[1][:, idx], leaves[2][:, idx], lens, dh ** -0.5, W, slopes.double().to(q.device),
-                            None if mems[0] is None else mems[0][idx], None if mems[1] is None else mems[1][idx], bool(Z),
-                            keep, keep_mem, fill=fill)
-    (o * do.double()).sum().backward()
-    lse = lse.detach().clone()
-    if not sinks:
-        dead = ~visible(n, lens, W).any(-1)[:, 0]   # [b][n]
-        lse.transpose(1, 2)[dead] = 0.
-    out = dict(o=o, lse=lse, dq=leaves[0].grad, dk=leaves[1].grad, dv=leaves[2].grad)
-    if mems[0] is not None:
-        out.update(dmk=mems[0].grad, dmv=mems[1].grad)
-    return {name: t.detach().cpu() for name, t in out.items()}
 
 
 @pytest.mark.parametrize('M,Z', SINKS)
@@ -114,9 +50,9 @@ def test_alibi_forward_and_backward_against_fp64(b, H, Hkv, n, dh, W, M, Z):
     q, k, v, do, lens, *mem = problem(b, H, n, dh, n + dh + Hkv + (W or 0) + M, Hkv=Hkv, M=M)
     mem_k, mem_v = mem or (None, None)
     slopes = dev_slopes(H)
-    ref = alibi_ref(q, k, v, do, lens, W, slopes, mem_k, mem_v, Z)
+    ref = alibi_ref(q, k, v, do, lens, W, (slopes,), mem_k, mem_v, Z)
     for mode in modes_of(n, dh):
-        res = alibi_lib(q, k, v, lens, do, dh ** -0.5, 0., mode, slopes, W=W, mem_k=mem_k, mem_v=mem_v, Z=Z)
+        res = alibi_lib(q, k, v, lens, do, dh ** -0.5, 0., mode, slopes=slopes, W=W, mem_k=mem_k, mem_v=mem_v, Z=Z)
         for name, t in res.items():
             assert torch.isfinite(t).all(), (mode, name)
         assert res['dk'].shape == (b, Hkv, n, dh) and (M == 0 or res['dmk'].shape == (Hkv, M, dh))
@@ -132,11 +68,11 @@ def test_alibi_num_heads_leaves_the_other_heads_without_bias(M, Z):
     mem_k, mem_v = mem or (None, None)
     slopes = dev_slopes(H, 2)
     assert slopes.tolist() == [2. ** -4, 2. ** -8, 0., 0.]
-    ref = alibi_ref(q, k, v, do, lens, W, slopes, mem_k, mem_v, Z)
-    plain = alibi_ref(q, k, v, do, lens, W, torch.zeros(H), mem_k, mem_v, Z)
+    ref = alibi_ref(q, k, v, do, lens, W, (slopes,), mem_k, mem_v, Z)
+    plain = alibi_ref(q, k, v, do, lens, W, (torch.zeros(H),), mem_k, mem_v, Z)
     assert not torch.allclose(ref['o'][:, :2], plain['o'][:, :2], atol=1e-3)
     for mode in modes_of(n, dh):
-        res = alibi_lib(q, k, v, lens, do, dh ** -0.5, 0., mode, slopes, W=W, mem_k=mem_k, mem_v=mem_v, Z=Z)
+        res = alibi_lib(q, k, v, lens, do, dh ** -0.5, 0., mode, slopes=slopes, W=W, mem_k=mem_k, mem_v=mem_v, Z=Z)
         check_ref(res, ref)
         G.tol(res['o'][:, 2:], plain['o'][:, 2:], 1e-5, 1e-5)
         G.tol(res['lse'][:, 2:], plain['lse'][:, 2:], 1e-5, 1e-5)
@@ -155,7 +91,7 @@ def test_alibi_entry_points_with_null_slopes_are_the_sink_ones(p, n, W):
         kw = dict(W=W, mem_k=mem[0], mem_v=mem[1], Z=1) if M else dict(W=W)
         for mode in modes_of(n, dh):
             old = sink_lib(q, k, v, lens, do, dh ** -0.5, p, mode, **kw)
-            new = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, mode, None, **kw)
+            new = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, mode, **kw)
             assert set(old) == set(new) and set(new) >= set(NAMES)
             for name in old:
                 assert torch.equal(old[name], new[name]), (Hkv, M, mode, name)
@@ -169,8 +105,8 @@ def test_alibi_backward_repeats_bit_for_bit(p, Hkv, n, W):
     q, k, v, do, lens, mem_k, mem_v = problem(b, H, n, dh, n + Hkv, Hkv=Hkv, M=3)
     slopes = dev_slopes(H)
     for mode in modes_of(n, dh):
-        one = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, mode, slopes, W=W, mem_k=mem_k, mem_v=mem_v, Z=1)
-        two = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, mode, slopes, W=W, mem_k=mem_k, mem_v=mem_v, Z=1)
+        one = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, mode, slopes=slopes, W=W, mem_k=mem_k, mem_v=mem_v, Z=1)
+        two = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, mode, slopes=slopes, W=W, mem_k=mem_k, mem_v=mem_v, Z=1)
         for name in one:
             assert torch.isfinite(one[name]).all() and torch.equal(one[name], two[name]), (mode, name)
 
@@ -193,7 +129,7 @@ def test_alibi_dropout_against_host_keep_bits(p, Hkv, n, W, M):
     slopes = ops.alibi_slopes(H)
     keep = torch.from_numpy(P.attn_dropout_keep(b, H, n, p, seed, offset, layer)).double() / (1 - p)
     keep_mem = torch.from_numpy(sink_dropout_keep(b, H, n, M, p, seed, offset, layer)).double() / (1 - p) if M else None
-    ref = alibi_ref(q, k, v, do, lens, W, slopes, mem_k, mem_v, bool(M), keep, keep_mem)
+    ref = alibi_ref(q, k, v, do, lens, W, (slopes,), mem_k, mem_v, bool(M), keep, keep_mem)
     names = ('dq', 'dk', 'dv') + (('dmk', 'dmv') if M else ())
     leaves = [t.to(DEV).requires_grad_() for t in ((q, k, v, mem_k, mem_v) if M else (q, k, v))]
     out = ops.attention(*leaves[:3], lens.to(DEV), dh ** -0.5, p, seed=seed, offset=offset, sub=layer, window=W or 0,
@@ -217,8 +153,8 @@ def test_alibi_dead_rows_are_the_uniform_average(p):
     b, H, Hkv, n, dh, W = 2, 4, 2, 130, 16, 10
     q, k, v, do, lens = problem(b, H, n, dh, 5, Hkv=Hkv)
     assert int(lens[b - 1]) == 1
-    a = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, 'two', dev_slopes(H), W=W)
-    z = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, 'two', None, W=W)
+    a = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, 'two', slopes=dev_slopes(H), W=W)
+    z = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, 'two', W=W)
     dead = slice(1 + W, n)
     assert torch.equal(a['o'][b - 1, :, dead], z['o'][b - 1, :, dead])
     assert not torch.equal(a['o'][0], z['o'][0])

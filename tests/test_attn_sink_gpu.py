@@ -24,6 +24,7 @@ pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 gqa_lib = functools.partial(AH.attn_lib, abi='gqa')
 sink_lib = functools.partial(AH.attn_lib, abi='sink')   # mem_k None: M = 0 (null sink pointers)
+sink_ref = functools.partial(AH.fp64_ref, attn_sink_ref)   # extra = ()
 SHAPES = [(3, 4, 4, 37, 16, None), (2, 4, 2, 70, 16, None), (2, 4, 2, 130, 16, 10), (2, 4, 1, 200, 16, 64),
           (2, 6, 2, 64, 32, 7), (1, 4, 2, 70, 64, None)]
 SINKS = [(0, 1), (1, 0), (3, 1), (16, 0)]
@@ -32,25 +33,6 @@ SINKS = [(0, 1), (1, 0), (3, 1), (16, 0)]
 # ----------------------------------------------------------------------------------------------
 # kernel level
 # ----------------------------------------------------------------------------------------------
-
-
-def sink_ref(q, k, v, do, lens, W, mem_k, mem_v, Z, keep=None, keep_mem=None):
-    """The fp64 reference (test_attn_sink_cpu.attn_sink_ref) on k, v and the memory rows repeated to the
-    query heads by ops.kv_head_index; autograd sums dk / dv / dmem over each kv head's query heads.
-    Returns a dict of CPU tensors: o, lse, dq, dk, dv (and dmk, dmv)."""
-    from xtrl_amd import ops
-    H, Hkv, dh = q.shape[1], k.shape[1], q.shape[3]
-    idx = ops.kv_head_index(H, Hkv, device=k.device)
-    leaves = [t.double().requires_grad_() for t in (q, k, v)]
-    mems = [t.double().requires_grad_() for t in (mem_k, mem_v)] if mem_k is not None else [None, None]
-    o, lse = attn_sink_ref(leaves[0], leaves[1][:, idx], leaves[2][:, idx], lens, dh ** -0.5, W,
-                           None if mems[0] is None else mems[0][idx], None if mems[1] is None else mems[1][idx], bool(Z),
-                           keep, keep_mem)
-    (o * do.double()).sum().backward()
-    out = dict(o=o, lse=lse, dq=leaves[0].grad, dk=leaves[1].grad, dv=leaves[2].grad)
-    if mems[0] is not None:
-        out.update(dmk=mems[0].grad, dmv=mems[1].grad)
-    return {n: t.detach().cpu() for n, t in out.items()}
 
 
 @pytest.mark.parametrize('M,Z', SINKS)
@@ -62,7 +44,7 @@ def test_sink_forward_and_backward_against_fp64(b, H, Hkv, n, dh, W, M, Z):
     the zero key only their o is exactly 0 — and whatever their dO, they add nothing to dK / dV."""
     q, k, v, do, lens, *mem = problem(b, H, n, dh, n + dh + Hkv + (W or 0) + M, Hkv=Hkv, M=M)
     mem_k, mem_v = mem or (None, None)
-    ref = sink_ref(q, k, v, do, lens, W, mem_k, mem_v, Z)
+    ref = sink_ref(q, k, v, do, lens, W, (), mem_k, mem_v, Z)
     for mode in modes_of(n, dh):
         res = sink_lib(q, k, v, lens, do, dh ** -0.5, 0., mode, W=W, mem_k=mem_k, mem_v=mem_v, Z=Z)
         for name, t in res.items():
@@ -128,7 +110,7 @@ def test_sink_dropout_against_host_keep_bits(p, Hkv, n, W):
     seed, offset, layer = 1234567, 5, 3
     keep = torch.from_numpy(P.attn_dropout_keep(b, H, n, p, seed, offset, layer)).double() / (1 - p)
     keep_mem = torch.from_numpy(sink_dropout_keep(b, H, n, M, p, seed, offset, layer)).double() / (1 - p)
-    ref = sink_ref(q, k, v, do, lens, W, mem_k, mem_v, 1, keep, keep_mem)
+    ref = sink_ref(q, k, v, do, lens, W, (), mem_k, mem_v, 1, keep, keep_mem)
     leaves = [t.to(DEV).requires_grad_() for t in (q, k, v, mem_k, mem_v)]
     out = ops.attention(*leaves[:3], lens.to(DEV), dh ** -0.5, p, seed=seed, offset=offset, sub=layer, window=W or 0,
                         mem_k=leaves[3], mem_v=leaves[4], add_zero_kv=True)

@@ -7,6 +7,8 @@ values the C ABI refuses; then the rollout (both decode paths, the second 128-ke
 fused out-projection form), the padded and the packed learn step, the deploy forward and the reference-mode
 autograd step against the soft-clamp oracle (test_attn_softclamp_cpu.softclamp_forward installed over the frozen
 oracle's Attention)."""
+import functools
+
 import pytest
 import torch
 
@@ -14,7 +16,7 @@ from oracle import philox as P
 
 import attn_harness as AH
 import test_gpu_parity as G
-from attn_harness import NAMES, check_ref, fused_bwd, modes_of, problem
+from attn_harness import NAMES, check_ref, modes_of, problem
 from test_attn_alibi_gpu import SHAPES, SINKS, alibi_lib, dev_slopes
 from test_attn_softclamp_cpu import attn_softclamp_ref, install_softclamp
 from test_attn_sink_cpu import sink_dropout_keep, visible
@@ -24,81 +26,13 @@ DEV = 'cuda'
 # (c, the factor on q — and on mem_k): c = 2 with q x 4 — about 30 % of the visible scores saturated (|x / c| > 2),
 # about 12 % linear (|x / c| < 0.3) — and the default c = 50 on unscaled scores, the near-linear regime
 REGIMES = {'c2-q4': (2., 4.), 'c50': (50., 1.)}
+softclamp_lib = functools.partial(AH.attn_lib, abi='softclamp')   # slopes=None: a NULL pointer; c=0.: off
+softclamp_ref = functools.partial(AH.fp64_ref, attn_softclamp_ref)   # extra = (slopes or None, c)
 
 
 # ----------------------------------------------------------------------------------------------
 # kernel level
 # ----------------------------------------------------------------------------------------------
-
-
-def softclamp_lib(q, k, v, lens, do, scale, p, mode, slopes, c, W=None, mem_k=None, mem_v=None, Z=False, seed=3,
-                  offset=1, sub=0):
-    """test_attn_alibi_gpu.alibi_lib through xtrl_attn_fwd_softclamp / xtrl_attn_bwd_softclamp /
-    xtrl_attn_bwd_part_softclamp: ``c`` is the float after the slopes (0: off), ``slopes`` [H] fp32 on the device
-    or None (a NULL pointer).  Every output and workspace NaN before the calls.  Returns o, lse, delta, dq, dk,
-    dv (and dmk, dmv at M > 0)."""
-    from xtrl_amd import _lib as L
-    lib = L.lib()
-    b, H, n, dh = q.shape
-    Hkv = k.shape[1]
-    M = 0 if mem_k is None else mem_k.shape[1]
-    assert mode in ('two', 'fused', 'part'), mode
-    assert slopes is None or (slopes.shape == (H,) and slopes.dtype == torch.float32 and slopes.is_cuda), slopes
-    nan = lambda *s: torch.full(s, float('nan'), device=DEV)   # noqa: E731
-    o, dq, dk, dv = nan(*q.shape), nan(*q.shape), nan(*k.shape), nan(*v.shape)
-    lse, delta = nan(b, H, n), nan(b, H, n)
-    res = dict(o=o, lse=lse, delta=delta, dq=dq, dk=dk, dv=dv)
-    tail = (b, H, Hkv, n, dh, scale, p, seed, offset, sub, int(W or 0), M, int(Z), L.ptr(slopes), float(c), L.stream())
-    nws = int(lib.xtrl_attn_sink_ws_floats(b, H, M, dh))
-    dmk, dmv, ws = (nan(Hkv, M, dh), nan(Hkv, M, dh), nan(nws)) if M else (None, None, None)
-    fwd_sink = (L.ptr(mem_k), L.ptr(mem_v))
-    bwd_sink = fwd_sink + (L.ptr(dmk), L.ptr(dmv), L.ptr(ws), nws)
-    if M:
-        res.update(dmk=dmk, dmv=dmv)
-    io = tuple(L.ptr(t) for t in (q, k, v, lens, o, lse))
-    try:
-        L.check(lib.xtrl_attn_fwd_softclamp(*io, *fwd_sink, *tail), 'attn_fwd_softclamp')
-        grads = tuple(L.ptr(t) for t in (do, dq, dk, dv, delta))
-        with fused_bwd(mode != 'two'):
-            if mode == 'part':
-                nf = int(lib.xtrl_attn_bwd_part_floats(b, H, n, dh))
-                part = nan(nf)
-                L.check(lib.xtrl_attn_bwd_part_softclamp(*io, *grads, L.ptr(part), nf, *bwd_sink, *tail),
-                        'attn_bwd_part_softclamp')
-            else:
-                L.check(lib.xtrl_attn_bwd_softclamp(*io, *grads, *bwd_sink, *tail), 'attn_bwd_softclamp')
-    finally:
-        torch.cuda.synchronize()
-        softclamp_lib.last = res
-    return res
-
-
-def softclamp_ref(q, k, v, do, lens, W, slopes, c, mem_k=None, mem_v=None, Z=False, keep=None, keep_mem=None):
-    """The fp64 reference (test_attn_softclamp_cpu.attn_softclamp_ref; the fp32 slopes widened, None: no bias) on
-    k, v and the memory rows repeated to the query heads; autograd sums dk / dv / dmem over each kv head's query
-    heads.  Without a sink the masked scores take x-transformers' finite fill, so the dead rows of a window are
-    uniform over all n positions; their lse is set to the kernels' convention for such rows, 0.
-    Returns a dict of CPU tensors: o, lse, dq, dk, dv (and dmk, dmv)."""
-    from xtrl_amd import ops
-    H, Hkv, n, dh = q.shape[1], k.shape[1], q.shape[2], q.shape[3]
-    idx = ops.kv_head_index(H, Hkv, device=k.device)
-    leaves = [t.double().requires_grad_() for t in (q, k, v)]
-    mems = [t.double().requires_grad_() for t in (mem_k, mem_v)] if mem_k is not None else [None, None]
-    sinks = mem_k is not None or bool(Z)
-    fill = float('-inf') if sinks else -torch.finfo(torch.float64).max
-    o, lse = attn_softclamp_ref(leaves[0], leaves[1][:, idx], leaves[2][:, idx], lens, dh ** -0.5, W,
-                                None if slopes is None else slopes.double().to(q.device), float(c),
-                                None if mems[0] is None else mems[0][idx], None if mems[1] is None else mems[1][idx],
-                                bool(Z), keep, keep_mem, fill=fill)
-    (o * do.double()).sum().backward()
-    lse = lse.detach().clone()
-    if not sinks:
-        dead = ~visible(n, lens, W).any(-1)[:, 0]   # [b][n]
-        lse.transpose(1, 2)[dead] = 0.
-    out = dict(o=o, lse=lse, dq=leaves[0].grad, dk=leaves[1].grad, dv=leaves[2].grad)
-    if mems[0] is not None:
-        out.update(dmk=mems[0].grad, dmv=mems[1].grad)
-    return {name: t.detach().cpu() for name, t in out.items()}
 
 
 @pytest.mark.parametrize('regime', list(REGIMES))
@@ -120,9 +54,9 @@ def test_softclamp_forward_and_backward_against_fp64(b, H, Hkv, n, dh, W, M, Z, 
     if M:
         mem_k = mem_k * f
     slopes = dev_slopes(H) if alibi else None
-    ref = softclamp_ref(q, k, v, do, lens, W, slopes, c, mem_k, mem_v, Z)
+    ref = softclamp_ref(q, k, v, do, lens, W, (slopes, c), mem_k, mem_v, Z)
     for mode in modes_of(n, dh):
-        res = softclamp_lib(q, k, v, lens, do, dh ** -0.5, 0., mode, slopes, c, W=W, mem_k=mem_k, mem_v=mem_v, Z=Z)
+        res = softclamp_lib(q, k, v, lens, do, dh ** -0.5, 0., mode, slopes=slopes, c=c, W=W, mem_k=mem_k, mem_v=mem_v, Z=Z)
         for name, t in res.items():
             assert torch.isfinite(t).all(), (mode, name)
         assert res['dk'].shape == (b, Hkv, n, dh) and (M == 0 or res['dmk'].shape == (Hkv, M, dh))
@@ -143,8 +77,8 @@ def test_softclamp_reference_regimes_bite():
     x = torch.einsum('bhid,bhjd->bhij', q.double() * f, kk) * dh ** -0.5
     y = (x / c).abs()[visible(n, lens, W).expand(b, H, n, n)]
     assert float((y > 2).double().mean()) > 0.2 and float((y < 0.3).double().mean()) > 0.05
-    on = softclamp_ref(q * f, k, v, do, lens, W, None, c)
-    off = softclamp_ref(q * f, k, v, do, lens, W, None, 1e9)
+    on = softclamp_ref(q * f, k, v, do, lens, W, (None, c))
+    off = softclamp_ref(q * f, k, v, do, lens, W, (None, 1e9))
     assert float((on['o'] - off['o']).abs().max()) > 1e-2 and float((on['dq'] - off['dq']).abs().max()) > 1e-2
 
 
@@ -161,8 +95,8 @@ def test_softclamp_entry_points_at_zero_are_the_alibi_ones(p, n, W):
         kw = dict(W=W, mem_k=mem[0], mem_v=mem[1], Z=1) if M else dict(W=W)
         for slopes in (dev_slopes(H), None):
             for mode in modes_of(n, dh):
-                old = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, mode, slopes, **kw)
-                new = softclamp_lib(q, k, v, lens, do, dh ** -0.5, p, mode, slopes, 0., **kw)
+                old = alibi_lib(q, k, v, lens, do, dh ** -0.5, p, mode, slopes=slopes, **kw)
+                new = softclamp_lib(q, k, v, lens, do, dh ** -0.5, p, mode, slopes=slopes, c=0., **kw)
                 assert set(old) == set(new) and set(new) >= set(NAMES)
                 for name in old:
                     assert torch.equal(old[name], new[name]), (Hkv, M, slopes is None, mode, name)
@@ -176,8 +110,8 @@ def test_softclamp_backward_repeats_bit_for_bit(p, Hkv, n, W):
     q, k, v, do, lens, mem_k, mem_v = problem(b, H, n, dh, n + Hkv, Hkv=Hkv, M=3)
     slopes = dev_slopes(H)
     for mode in modes_of(n, dh):
-        one = softclamp_lib(q * 4, k, v, lens, do, dh ** -0.5, p, mode, slopes, 2., W=W, mem_k=mem_k, mem_v=mem_v, Z=1)
-        two = softclamp_lib(q * 4, k, v, lens, do, dh ** -0.5, p, mode, slopes, 2., W=W, mem_k=mem_k, mem_v=mem_v, Z=1)
+        one = softclamp_lib(q * 4, k, v, lens, do, dh ** -0.5, p, mode, slopes=slopes, c=2., W=W, mem_k=mem_k, mem_v=mem_v, Z=1)
+        two = softclamp_lib(q * 4, k, v, lens, do, dh ** -0.5, p, mode, slopes=slopes, c=2., W=W, mem_k=mem_k, mem_v=mem_v, Z=1)
         for name in one:
             assert torch.isfinite(one[name]).all() and torch.equal(one[name], two[name]), (mode, name)
 
@@ -201,7 +135,7 @@ def test_softclamp_dropout_against_host_keep_bits(p, Hkv, n, W, M):
     slopes = ops.alibi_slopes(H)
     keep = torch.from_numpy(P.attn_dropout_keep(b, H, n, p, seed, offset, layer)).double() / (1 - p)
     keep_mem = torch.from_numpy(sink_dropout_keep(b, H, n, M, p, seed, offset, layer)).double() / (1 - p) if M else None
-    ref = softclamp_ref(q, k, v, do, lens, W, slopes, c, mem_k, mem_v, bool(M), keep, keep_mem)
+    ref = softclamp_ref(q, k, v, do, lens, W, (slopes, c), mem_k, mem_v, bool(M), keep, keep_mem)
     names = ('dq', 'dk', 'dv') + (('dmk', 'dmv') if M else ())
     leaves = [t.to(DEV).requires_grad_() for t in ((q, k, v, mem_k, mem_v) if M else (q, k, v))]
     out = ops.attention(*leaves[:3], lens.to(DEV), dh ** -0.5, p, seed=seed, offset=offset, sub=layer, window=W or 0,
@@ -226,8 +160,8 @@ def test_softclamp_dead_rows_are_the_uniform_average(p):
     b, H, Hkv, n, dh, W = 2, 4, 2, 130, 16, 10
     q, k, v, do, lens = problem(b, H, n, dh, 5, Hkv=Hkv)
     assert int(lens[b - 1]) == 1
-    a = softclamp_lib(q * 4, k, v, lens, do, dh ** -0.5, p, 'two', None, 2., W=W)
-    z = softclamp_lib(q * 4, k, v, lens, do, dh ** -0.5, p, 'two', None, 0., W=W)
+    a = softclamp_lib(q * 4, k, v, lens, do, dh ** -0.5, p, 'two', c=2., W=W)
+    z = softclamp_lib(q * 4, k, v, lens, do, dh ** -0.5, p, 'two', c=0., W=W)
     dead = slice(1 + W, n)
     assert torch.equal(a['o'][b - 1, :, dead], z['o'][b - 1, :, dead])
     assert not torch.equal(a['o'][0], z['o'][0])
@@ -248,11 +182,11 @@ def test_softclamp_c_abi_refuses_a_negative_or_non_finite_value(bad):
     b, H, Hkv, n, dh = 2, 4, 2, 37, 16
     q, k, v, do, lens = problem(b, H, n, dh, 7, Hkv=Hkv)
     with pytest.raises(RuntimeError, match='softclamp') as ei:
-        softclamp_lib(q, k, v, lens, do, dh ** -0.5, 0., 'two', None, bad)
+        softclamp_lib(q, k, v, lens, do, dh ** -0.5, 0., 'two', c=bad)
     want = {-1.: 'softclamp -1 ', -1e-30: 'softclamp -1e-30 ', float('inf'): 'softclamp inf ', float('-inf'): 'softclamp -inf '}
     msg = str(ei.value).lower()
     assert ('nan' in msg) if bad != bad else (want[bad] in msg), msg
-    for t in softclamp_lib.last.values():
+    for t in AH.attn_lib.last.values():
         assert torch.isnan(t).all()
     lib = L.lib()
     nan = lambda *s: torch.full(s, float('nan'), device=DEV)   # noqa: E731

@@ -1123,32 +1123,36 @@ int sink_bwd(AttnArgs& a, const AttnProblem& p, hipStream_t s) {
   a.dMK = p.dmem_k;
   a.dMV = p.dmem_v;
   a.dm_accum = p.dmem_accum;
-  if (p.softclamp > 0.f) {
-    if (p.dh == 16) hipLaunchKernelGGL((k_attn_sink_bwd<16, true>), dim3(p.b * p.H), dim3(256), 0, s, a);
-    else if (p.dh == 32) hipLaunchKernelGGL((k_attn_sink_bwd<32, true>), dim3(p.b * p.H), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_sink_bwd<64, true>), dim3(p.b * p.H), dim3(256), 0, s, a);
-  } else if (p.dh == 16) hipLaunchKernelGGL(k_attn_sink_bwd<16>, dim3(p.b * p.H), dim3(256), 0, s, a);
-  else if (p.dh == 32) hipLaunchKernelGGL(k_attn_sink_bwd<32>, dim3(p.b * p.H), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_attn_sink_bwd<64>, dim3(p.b * p.H), dim3(256), 0, s, a);
+  if (p.softclamp > 0.f) XTRL_LAUNCH_DH(p.dh, k_attn_sink_bwd, (true), dim3(p.b * p.H), dim3(256), 0, s, a);
+  else XTRL_LAUNCH_DH(p.dh, k_attn_sink_bwd, (false), dim3(p.b * p.H), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_attn_sink_reduce, dim3((a.Hkv * p.mem_kv * p.dh + 255) / 256), dim3(256), 0, s, a, p.b, p.dh);
   XTRL_LAUNCHED("attn_sink_bwd");
   return XTRL_OK;
 }
 
-// dh dispatch of a kernel template with a trailing GQA parameter: <dh, false> for one kv head per query
-// head — the instantiations of before — and <dh, true> for Hkv < H
-#define XTRL_ATTN_LAUNCH_DH(KERNEL, gqa, dh, grid)                                                          \
-  do {                                                                                                      \
-    if (gqa) {                                                                                              \
-      if ((dh) == 16) hipLaunchKernelGGL((KERNEL<16, true>), grid, dim3(256), 0, s, a);                     \
-      else if ((dh) == 32) hipLaunchKernelGGL((KERNEL<32, true>), grid, dim3(256), 0, s, a);                \
-      else hipLaunchKernelGGL((KERNEL<64, true>), grid, dim3(256), 0, s, a);                                \
-    } else {                                                                                                \
-      if ((dh) == 16) hipLaunchKernelGGL((KERNEL<16, false>), grid, dim3(256), 0, s, a);                    \
-      else if ((dh) == 32) hipLaunchKernelGGL((KERNEL<32, false>), grid, dim3(256), 0, s, a);               \
-      else hipLaunchKernelGGL((KERNEL<64, false>), grid, dim3(256), 0, s, a);                               \
-    }                                                                                                       \
-  } while (0)
+// the sum of the per-key-tile dQ partials that k_attn_bwd_dkdv<16, true, ...> left in a.dQp
+void dq_reduce(const AttnArgs& a, const AttnProblem& p, hipStream_t s) {
+  const int64_t units = (int64_t)p.b * p.H * p.n * 4;
+  hipLaunchKernelGGL(k_attn_dq_reduce<16>, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, a, p.b * p.H);
+}
+
+// The general forms of the backward — GQA, on it ALiBi, on that the soft-clamp — take the kv head mapping
+// and the window at run time.  The dK / dV grid is over the kv heads (the group loop; a.Hkv = H without
+// grouped-query attention: a group of one query head per kv head), the dQ side stays per query head.  The
+// one-launch fused backward has no group loop: `part` (dh = 16, the caller gave the dQ partial workspace)
+// takes the dK / dV kernel with the dQ pass folded in, else the kernel pair
+template <bool ALIBI, bool CAP>
+void bwd_general(AttnArgs& a, const AttnProblem& p, bool part, dim3 grid, hipStream_t s) {
+  dim3 kgrid((p.n + TK - 1) / TK, p.b * a.Hkv);
+  if (part) {
+    a.dQp = p.dq_part;
+    hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, true, true, ALIBI, CAP>), kgrid, dim3(256), 0, s, a);
+    dq_reduce(a, p, s);
+  } else {
+    XTRL_LAUNCH_DH(p.dh, k_attn_bwd_dkdv, (false, true, true, ALIBI, CAP), kgrid, dim3(256), 0, s, a);
+    XTRL_LAUNCH_DH(p.dh, k_attn_bwd_dq, (true, ALIBI, CAP), grid, dim3(256), 0, s, a);
+  }
+}
 
 }  // namespace
 
@@ -1167,37 +1171,28 @@ int attn_fwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   a.OGout = og;
   const bool gqa = is_gqa(p);
   dim3 grid((p.n + TQ - 1) / TQ, p.b * p.H);
-  if (p.softclamp > 0.f) {   // the soft-clamp forms (the ALiBi ones plus the clamp; slopes or none)
-    if (attn_has_sinks(p)) {
-      if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, true, true, true>), grid, dim3(256), 0, s, a);
-      else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, true, true, true>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_attn_fwd<64, true, true, true, true>), grid, dim3(256), 0, s, a);
-    } else {
-      if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, false, true, true>), grid, dim3(256), 0, s, a);
-      else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, false, true, true>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_attn_fwd<64, true, false, true, true>), grid, dim3(256), 0, s, a);
-    }
-  } else if (p.alibi) {   // the ALiBi forms (two per dh: with and without sinks; both take the kv head mapping at run time)
-    if (attn_has_sinks(p)) {
-      if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, true, true>), grid, dim3(256), 0, s, a);
-      else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, true, true>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_attn_fwd<64, true, true, true>), grid, dim3(256), 0, s, a);
-    } else {
-      if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, false, true>), grid, dim3(256), 0, s, a);
-      else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, false, true>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_attn_fwd<64, true, false, true>), grid, dim3(256), 0, s, a);
-    }
-  } else if (attn_has_sinks(p)) {   // the sink form (one per dh: it takes the kv head mapping at run time, Hkv = H included)
-    if (p.dh == 16) hipLaunchKernelGGL((k_attn_fwd<16, true, true>), grid, dim3(256), 0, s, a);
-    else if (p.dh == 32) hipLaunchKernelGGL((k_attn_fwd<32, true, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_fwd<64, true, true>), grid, dim3(256), 0, s, a);
-  } else {
-    XTRL_ATTN_LAUNCH_DH(k_attn_fwd, gqa, p.dh, grid);
+  const bool sinks = attn_has_sinks(p);
+  // k_attn_fwd<DH, GQA, SINK, ALIBI, CAP>: every form from the sink one up takes the kv head mapping at run
+  // time (Hkv = H included); the ALiBi and soft-clamp forms come with and without sinks, the soft-clamp
+  // ones with slopes or none
+  switch (attn_form(p.softclamp > 0.f, p.alibi != nullptr, sinks, gqa)) {
+    case ATTN_CLAMP:
+      if (sinks) XTRL_LAUNCH_DH(p.dh, k_attn_fwd, (true, true, true, true), grid, dim3(256), 0, s, a);
+      else XTRL_LAUNCH_DH(p.dh, k_attn_fwd, (true, false, true, true), grid, dim3(256), 0, s, a);
+      break;
+    case ATTN_ALIBI:
+      if (sinks) XTRL_LAUNCH_DH(p.dh, k_attn_fwd, (true, true, true), grid, dim3(256), 0, s, a);
+      else XTRL_LAUNCH_DH(p.dh, k_attn_fwd, (true, false, true), grid, dim3(256), 0, s, a);
+      break;
+    case ATTN_SINK: XTRL_LAUNCH_DH(p.dh, k_attn_fwd, (true, true), grid, dim3(256), 0, s, a); break;
+    case ATTN_GQA: XTRL_LAUNCH_DH(p.dh, k_attn_fwd, (true), grid, dim3(256), 0, s, a); break;
+    case ATTN_PLAIN: XTRL_LAUNCH_DH(p.dh, k_attn_fwd, (false), grid, dim3(256), 0, s, a); break;
   }
   XTRL_LAUNCHED("attn_fwd");
   if (has_dead_rows(p)) {
     dim3 dgrid((p.n + 256 / p.dh - 1) / (256 / p.dh), p.b * p.H);
-    XTRL_ATTN_LAUNCH_DH(k_attn_dead_fwd, gqa, p.dh, dgrid);
+    if (gqa) XTRL_LAUNCH_DH(p.dh, k_attn_dead_fwd, (true), dgrid, dim3(256), 0, s, a);
+    else XTRL_LAUNCH_DH(p.dh, k_attn_dead_fwd, (false), dgrid, dim3(256), 0, s, a);
     XTRL_LAUNCHED("attn_dead_fwd");
   }
   return XTRL_OK;
@@ -1225,84 +1220,34 @@ int attn_bwd_ex(const AttnProblem& p, const float* q, const float* k, const floa
   dim3 grid((p.n + TQ - 1) / TQ, p.b * p.H);
   const int64_t part_need = attn_dq_part_floats(p.b, p.H, p.n, p.dh);
   const bool gqa = is_gqa(p);
-  if (p.softclamp > 0.f) {
-    // soft-clamp: the ALiBi forms plus the clamp (slopes or none), under the same rule
-    dim3 kgrid((p.n + TK - 1) / TK, p.b * a.Hkv);
-    if (p.dh == 16 && p.dq_part && p.dq_part_floats >= part_need && attn_fused_bwd_on()) {
-      a.dQp = p.dq_part;
-      hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, true, true, true, true>), kgrid, dim3(256), 0, s, a);
-      const int64_t units = (int64_t)p.b * p.H * p.n * 4;
-      hipLaunchKernelGGL(k_attn_dq_reduce<16>, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, a, p.b * p.H);
-    } else if (p.dh == 16) {
-      hipLaunchKernelGGL((k_attn_bwd_dkdv<16, false, true, true, true, true>), kgrid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((k_attn_bwd_dq<16, true, true, true>), grid, dim3(256), 0, s, a);
-    } else if (p.dh == 32) {
-      hipLaunchKernelGGL((k_attn_bwd_dkdv<32, false, true, true, true, true>), kgrid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((k_attn_bwd_dq<32, true, true, true>), grid, dim3(256), 0, s, a);
-    } else {
-      hipLaunchKernelGGL((k_attn_bwd_dkdv<64, false, true, true, true, true>), kgrid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((k_attn_bwd_dq<64, true, true, true>), grid, dim3(256), 0, s, a);
-    }
-  } else if (p.alibi) {
-    // ALiBi: the GQA forms with the bias (a.Hkv = H without grouped-query attention: a group of one query
-    // head per kv head), under GQA's rule — no one-launch fused backward, the partial-workspace form when
-    // the caller gave the workspace, else the kernel pair
-    dim3 kgrid((p.n + TK - 1) / TK, p.b * a.Hkv);
-    if (p.dh == 16 && p.dq_part && p.dq_part_floats >= part_need && attn_fused_bwd_on()) {
-      a.dQp = p.dq_part;
-      hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, true, true, true>), kgrid, dim3(256), 0, s, a);
-      const int64_t units = (int64_t)p.b * p.H * p.n * 4;
-      hipLaunchKernelGGL(k_attn_dq_reduce<16>, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, a, p.b * p.H);
-    } else if (p.dh == 16) {
-      hipLaunchKernelGGL((k_attn_bwd_dkdv<16, false, true, true, true>), kgrid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((k_attn_bwd_dq<16, true, true>), grid, dim3(256), 0, s, a);
-    } else if (p.dh == 32) {
-      hipLaunchKernelGGL((k_attn_bwd_dkdv<32, false, true, true, true>), kgrid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((k_attn_bwd_dq<32, true, true>), grid, dim3(256), 0, s, a);
-    } else {
-      hipLaunchKernelGGL((k_attn_bwd_dkdv<64, false, true, true, true>), kgrid, dim3(256), 0, s, a);
-      hipLaunchKernelGGL((k_attn_bwd_dq<64, true, true>), grid, dim3(256), 0, s, a);
-    }
-  } else if (gqa) {
-    // Hkv < H: the dK / dV grid is over the kv heads (the group loop); the dQ side stays per query head.
-    // The one-launch fused backward has no group loop: short episodes take the long-episode form when
-    // the caller gave the dQ partial workspace, else the kernel pair
-    dim3 kgrid((p.n + TK - 1) / TK, p.b * p.Hkv);
-    if (p.dh == 16 && p.dq_part && p.dq_part_floats >= part_need && attn_fused_bwd_on()) {
-      a.dQp = p.dq_part;
-      hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, true, true>), kgrid, dim3(256), 0, s, a);
-      const int64_t units = (int64_t)p.b * p.H * p.n * 4;
-      hipLaunchKernelGGL(k_attn_dq_reduce<16>, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, a, p.b * p.H);
-    } else {
-      if (p.dh == 16) hipLaunchKernelGGL((k_attn_bwd_dkdv<16, false, true, true>), kgrid, dim3(256), 0, s, a);
-      else if (p.dh == 32) hipLaunchKernelGGL((k_attn_bwd_dkdv<32, false, true, true>), kgrid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_attn_bwd_dkdv<64, false, true, true>), kgrid, dim3(256), 0, s, a);
-      XTRL_ATTN_LAUNCH_DH(k_attn_bwd_dq, true, p.dh, grid);
-    }
-  } else if (p.dh == 16 && p.n <= FB_MAXN && attn_fused_bwd_on()) {   // short episodes: one fused launch
-    hipLaunchKernelGGL(k_attn_bwd_fused<16>, dim3(p.b * p.H), dim3(256), 0, s, a);
-  } else if (p.dh == 16 && p.dq_part && p.dq_part_floats >= part_need && attn_fused_bwd_on()) {
-    // long episodes: dK / dV with the dQ pass folded in (partials for multi-key-tile rows) + their sum
-    a.dQp = p.dq_part;
-    if (p.window > 0) hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, false>), grid, dim3(256), 0, s, a);
-    const int64_t units = (int64_t)p.b * p.H * p.n * 4;
-    hipLaunchKernelGGL(k_attn_dq_reduce<16>, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, a, p.b * p.H);
-  } else if (p.dh == 16) {
-    if (p.window > 0) hipLaunchKernelGGL(k_attn_bwd_dkdv<16>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_attn_bwd_dkdv<16, false, false>), grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_attn_bwd_dq<16>, grid, dim3(256), 0, s, a);
-  } else if (p.dh == 32) {
-    hipLaunchKernelGGL(k_attn_bwd_dkdv<32>, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_attn_bwd_dq<32>, grid, dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(k_attn_bwd_dkdv<64>, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_attn_bwd_dq<64>, grid, dim3(256), 0, s, a);
+  // XTRL_ATTN_FUSED_BWD=0 turns off both forms with the dQ pass folded in, the one launch and the partials
+  const bool fused_on = p.dh == 16 && attn_fused_bwd_on();
+  const bool part = fused_on && p.dq_part && p.dq_part_floats >= part_need;
+  // the sinks choose no form here: lse and o carry their share into the real keys' kernels, sink_bwd adds theirs
+  switch (attn_form(p.softclamp > 0.f, p.alibi != nullptr, false, gqa)) {
+    case ATTN_CLAMP: bwd_general<true, true>(a, p, part, grid, s); break;   // slopes or none
+    case ATTN_ALIBI: bwd_general<true, false>(a, p, part, grid, s); break;
+    case ATTN_GQA: bwd_general<false, false>(a, p, part, grid, s); break;
+    default:   // one kv head per query head, no option: the window is a template flag at dh = 16
+      if (fused_on && p.n <= FB_MAXN) {   // short episodes: one fused launch
+        hipLaunchKernelGGL(k_attn_bwd_fused<16>, dim3(p.b * p.H), dim3(256), 0, s, a);
+      } else if (part) {
+        // long episodes: dK / dV with the dQ pass folded in (partials for multi-key-tile rows) + their sum
+        a.dQp = p.dq_part;
+        if (p.window > 0) hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_attn_bwd_dkdv<16, true, false>), grid, dim3(256), 0, s, a);
+        dq_reduce(a, p, s);
+      } else {
+        if (p.dh == 16 && p.window <= 0) hipLaunchKernelGGL((k_attn_bwd_dkdv<16, false, false>), grid, dim3(256), 0, s, a);
+        else XTRL_LAUNCH_DH(p.dh, k_attn_bwd_dkdv, (false, true), grid, dim3(256), 0, s, a);
+        XTRL_LAUNCH_DH(p.dh, k_attn_bwd_dq, (false), grid, dim3(256), 0, s, a);
+      }
   }
   XTRL_LAUNCHED("attn_bwd");
   if (has_dead_rows(p)) {
-    dim3 dgrid((p.n + 256 / p.dh - 1) / (256 / p.dh), p.b * (gqa ? p.Hkv : p.H));
-    XTRL_ATTN_LAUNCH_DH(k_attn_dead_bwd, gqa, p.dh, dgrid);
+    dim3 dgrid((p.n + 256 / p.dh - 1) / (256 / p.dh), p.b * a.Hkv);
+    if (gqa) XTRL_LAUNCH_DH(p.dh, k_attn_dead_bwd, (true), dgrid, dim3(256), 0, s, a);
+    else XTRL_LAUNCH_DH(p.dh, k_attn_dead_bwd, (false), dgrid, dim3(256), 0, s, a);
     XTRL_LAUNCHED("attn_dead_bwd");
   }
   return sink_bwd(a, p, s);

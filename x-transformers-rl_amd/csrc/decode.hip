@@ -1447,19 +1447,20 @@ int launch_mlp(const XtrlDecodeDesc* D, int l, int t, hipStream_t s) {
                          last ? D->in_dim : D->d, s);
 }
 
-int launch_attn_decode(const XtrlDecodeDesc* D, int l, int t, hipStream_t s, const FrPost& fp = FrPost{}) {
-  const bool sinks = D->num_mem_kv > 0 || D->add_zero_kv;   // the SINK forms (checked by check_desc)
-  if (attn_fused(D, l)) {   // one workgroup of H waves per live row
+// the option form of the descriptor's attention (checked by check_desc).  No GQA rung: the decode kernels
+// take the kv head mapping at run time.  The sink forms serve ALiBi with or without sinks, the ALiBi
+// forms the soft-clamp with or without slopes
+AttnForm decode_attn_form(const XtrlDecodeDesc* D) {
+  return attn_form(D->attn_softclamp > 0.f, D->alibi_slopes != nullptr, D->num_mem_kv > 0 || D->add_zero_kv, false);
+}
+
+template <bool SINK, bool ALIBI, bool CAP>
+int launch_attn_decode_form(const XtrlDecodeDesc* D, int l, int t, hipStream_t s, const FrPost& fp) {
+  if (attn_fused(D, l)) {   // one workgroup of H waves per live row (dh = 16)
     const size_t lds = ((size_t)D->H * (D->Tmax + 3 * D->dh) + (size_t)D->H * D->d) * sizeof(float);
     const dim3 grid(D->E), blk(64 * D->H);
-    if (D->attn_softclamp > 0.f && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
-    else if (D->attn_softclamp > 0.f) hipLaunchKernelGGL((k_attn_decode<16, 1, true, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
-    else if (D->alibi_slopes && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
-    else if (D->alibi_slopes) hipLaunchKernelGGL((k_attn_decode<16, 1, true, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
-    else if (sinks && D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
-    else if (sinks) hipLaunchKernelGGL((k_attn_decode<16, 1, true>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
-    else if (D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
-    else hipLaunchKernelGGL((k_attn_decode<16, 1>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    if (D->d > 256) hipLaunchKernelGGL((k_attn_decode<16, 2, SINK, ALIBI, CAP>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
+    else hipLaunchKernelGGL((k_attn_decode<16, 1, SINK, ALIBI, CAP>), grid, blk, lds, s, *D, D->layers[l], l, t, fp);
     XTRL_LAUNCHED("attn_decode");
     return XTRL_OK;
   }
@@ -1467,26 +1468,18 @@ int launch_attn_decode(const XtrlDecodeDesc* D, int l, int t, hipStream_t s, con
   const size_t lds = 4 * (size_t)(D->Tmax + 3 * D->dh) * sizeof(float);
   XTRL_REQUIRE(lds <= 160 * 1024, "attn_decode: Tmax %d too large for LDS", D->Tmax);
   dim3 grid((waves + 3) / 4);
-  if (D->attn_softclamp > 0.f) {   // the soft-clamp forms (on the ALiBi ones, with or without slopes)
-    if (D->dh == 16) hipLaunchKernelGGL((k_attn_decode<16, 0, true, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-    else if (D->dh == 32) hipLaunchKernelGGL((k_attn_decode<32, 0, true, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-    else hipLaunchKernelGGL((k_attn_decode<64, 0, true, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-  } else if (D->alibi_slopes) {   // the ALiBi forms (on the SINK ones, with or without sinks)
-    if (D->dh == 16) hipLaunchKernelGGL((k_attn_decode<16, 0, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-    else if (D->dh == 32) hipLaunchKernelGGL((k_attn_decode<32, 0, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-    else hipLaunchKernelGGL((k_attn_decode<64, 0, true, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-  } else if (sinks) {
-    if (D->dh == 16) hipLaunchKernelGGL((k_attn_decode<16, 0, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-    else if (D->dh == 32) hipLaunchKernelGGL((k_attn_decode<32, 0, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-    else hipLaunchKernelGGL((k_attn_decode<64, 0, true>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-  } else if (D->dh == 16)
-    hipLaunchKernelGGL((k_attn_decode<16, 0>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-  else if (D->dh == 32)
-    hipLaunchKernelGGL((k_attn_decode<32, 0>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
-  else
-    hipLaunchKernelGGL((k_attn_decode<64, 0>), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
+  XTRL_LAUNCH_DH(D->dh, k_attn_decode, (0, SINK, ALIBI, CAP), grid, dim3(256), lds, s, *D, D->layers[l], l, t, fp);
   XTRL_LAUNCHED("attn_decode");
   return XTRL_OK;
+}
+
+int launch_attn_decode(const XtrlDecodeDesc* D, int l, int t, hipStream_t s, const FrPost& fp = FrPost{}) {
+  switch (decode_attn_form(D)) {
+    case ATTN_CLAMP: return launch_attn_decode_form<true, true, true>(D, l, t, s, fp);
+    case ATTN_ALIBI: return launch_attn_decode_form<true, true, false>(D, l, t, s, fp);
+    case ATTN_SINK: return launch_attn_decode_form<true, false, false>(D, l, t, s, fp);
+    default: return launch_attn_decode_form<false, false, false>(D, l, t, s, fp);
+  }
 }
 
 // one decode projection over the live rows of step t
@@ -2397,21 +2390,16 @@ int decode_step_rows(const XtrlDecodeDesc* D, int t, int max_rows, hipStream_t s
   const size_t lds = (size_t)row_lds(*D).tot * sizeof(float);
   if (hg.go) XTRL_REQUIRE(grid.x == 1 && D->act_host, "decode rows: the gated host step takes one row (E == 1) "
                                                        "and the pinned action buffer");
-  if (D->attn_softclamp > 0.f) {   // the soft-clamp forms (on the ALiBi ones, with or without slopes)
-    if (D->dh == 16) hipLaunchKernelGGL((k_decode_row<16, 2, true, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-    else if (D->dh == 32) hipLaunchKernelGGL((k_decode_row<32, 1, true, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-    else hipLaunchKernelGGL((k_decode_row<64, 1, true, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-  } else if (D->alibi_slopes) {   // the ALiBi forms (on the SINK ones, with or without sinks)
-    if (D->dh == 16) hipLaunchKernelGGL((k_decode_row<16, 2, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-    else if (D->dh == 32) hipLaunchKernelGGL((k_decode_row<32, 1, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-    else hipLaunchKernelGGL((k_decode_row<64, 1, true, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-  } else if (D->num_mem_kv > 0 || D->add_zero_kv) {   // the SINK forms
-    if (D->dh == 16) hipLaunchKernelGGL((k_decode_row<16, 2, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-    else if (D->dh == 32) hipLaunchKernelGGL((k_decode_row<32, 1, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-    else hipLaunchKernelGGL((k_decode_row<64, 1, true>), grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-  } else if (D->dh == 16) hipLaunchKernelGGL(k_decode_row<16>, grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-  else if (D->dh == 32) hipLaunchKernelGGL(k_decode_row<32>, grid, dim3(ROW_T), lds, s, *D, t, G, hg);
-  else hipLaunchKernelGGL(k_decode_row<64>, grid, dim3(ROW_T), lds, s, *D, t, G, hg);
+  // k_decode_row<DH, KP, SINK, ALIBI, CAP>, KP (two key passes at dh = 16) spelt out to reach the flags
+#define XTRL_ROW(...) \
+  XTRL_LAUNCH_DH(D->dh, k_decode_row, (DH == 16 ? 2 : 1, __VA_ARGS__), grid, dim3(ROW_T), lds, s, *D, t, G, hg)
+  switch (decode_attn_form(D)) {
+    case ATTN_CLAMP: XTRL_ROW(true, true, true); break;
+    case ATTN_ALIBI: XTRL_ROW(true, true); break;
+    case ATTN_SINK: XTRL_ROW(true); break;
+    default: XTRL_ROW(false); break;
+  }
+#undef XTRL_ROW
   XTRL_LAUNCHED("decode_row");
   return XTRL_OK;
 }

@@ -280,6 +280,30 @@ __host__ __device__ inline bool kv_head_owner(int h, int Hkv) {
 }
 int64_t attn_dq_part_floats(int b, int H, int n, int dh);
 
+// The option form of an attention launch (attn.hip, decode.hip).  The options are template flags on the
+// kernels, and each flag was added on top of the one before, so a launch picks the highest rung it needs
+// and names one template argument tuple for it — the flags are never combined freely (no cross product)
+enum AttnForm { ATTN_PLAIN, ATTN_GQA, ATTN_SINK, ATTN_ALIBI, ATTN_CLAMP };
+inline AttnForm attn_form(bool clamp, bool alibi, bool sinks, bool gqa) {
+  return clamp ? ATTN_CLAMP : alibi ? ATTN_ALIBI : sinks ? ATTN_SINK : gqa ? ATTN_GQA : ATTN_PLAIN;
+}
+
+// dh dispatch of a kernel template whose first parameter is the head size: launches KERNEL<DH, TAIL...>
+// for dh = 16 / 32 / 64 (checked by the caller).  TAIL, in parentheses, holds the template arguments after
+// DH; it may name DH.  After the launch geometry come the kernel's arguments
+#define XTRL_UNPAREN(...) __VA_ARGS__
+#define XTRL_LAUNCH_DH_(D, KERNEL, TAIL, ...)                                                     \
+  {                                                                                               \
+    constexpr int DH = D;                                                                         \
+    hipLaunchKernelGGL((KERNEL<DH, XTRL_UNPAREN TAIL>), __VA_ARGS__);                             \
+  }
+#define XTRL_LAUNCH_DH(dh, KERNEL, TAIL, grid, block, lds, stream, ...)                           \
+  do {                                                                                            \
+    if ((dh) == 16) XTRL_LAUNCH_DH_(16, KERNEL, TAIL, grid, block, lds, stream, __VA_ARGS__)      \
+    else if ((dh) == 32) XTRL_LAUNCH_DH_(32, KERNEL, TAIL, grid, block, lds, stream, __VA_ARGS__) \
+    else XTRL_LAUNCH_DH_(64, KERNEL, TAIL, grid, block, lds, stream, __VA_ARGS__)                 \
+  } while (0)
+
 // o (ungated) and lse; if gate != nullptr also og = o * sigmoid(gate) (og in the `out` layout)
 int attn_fwd_ex(const AttnProblem& p, const float* q, const float* k, const float* v, float* o, float* lse,
                 const float* gate, float* og, hipStream_t s);

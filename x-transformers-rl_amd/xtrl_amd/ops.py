@@ -222,11 +222,11 @@ class AttentionFn(torch.autograd.Function):
     reads kv head kv_head_index(H, Hkv)[h]; dk, dv come back [b][Hkv][n][dh], summed over each group).
     Attention sinks: mem_k, mem_v [Hkv][M][dh] (or None) and add_zero_kv join every row's softmax
     (include/xtrl_hip.h, xtrl_attn_fwd_sink); their gradients come back with dq, dk, dv.
-    ALiBi: alibi_slopes [H] fp32 (or None) subtracts slope[h] (i - j) from the real keys' scores
-    (xtrl_attn_fwd_alibi; no gradient).  Without slopes the calls are the _sink ones.
+    ALiBi: alibi_slopes [H] fp32 (or None) subtracts slope[h] (i - j) from the real keys' scores (no gradient).
     Logit soft-clamp: softclamp = c > 0 turns the real keys' and the memory columns' scores x (ALiBi term
-    included) into c tanh(x / c) before the masks (xtrl_attn_fwd_softclamp / xtrl_attn_bwd_softclamp, with
-    or without slopes); 0: off, the calls above."""
+    included) into c tanh(x / c) before the masks; 0: off.
+    One call path: xtrl_attn_fwd_softclamp / xtrl_attn_bwd_softclamp, which the narrower entry points forward
+    to with NULL slopes and softclamp 0."""
 
     @staticmethod
     def forward(ctx, q, k, v, lens, scale, dropout_p, seed, offset, sub, window=0, mem_k=None, mem_v=None,
@@ -253,14 +253,9 @@ class AttentionFn(torch.autograd.Function):
         args = (L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(mem_k) if M else None,
                 L.ptr(mem_v) if M else None, b, H, Hkv, n, dh, float(scale), float(dropout_p), int(seed), int(offset),
                 int(sub), int(window), M, int(bool(add_zero_kv)))
-        softclamp = float(softclamp)
-        if softclamp != 0.:   # (a negative or non-finite value is the library's to refuse)
-            L.check(lib.xtrl_attn_fwd_softclamp(*args, L.ptr(alibi_slopes) if alibi_slopes is not None else None,
-                                                softclamp, L.stream()), 'attn_fwd')
-        elif alibi_slopes is not None:
-            L.check(lib.xtrl_attn_fwd_alibi(*args, L.ptr(alibi_slopes), L.stream()), 'attn_fwd')
-        else:
-            L.check(lib.xtrl_attn_fwd_sink(*args, L.stream()), 'attn_fwd')
+        softclamp = float(softclamp)   # (a negative or non-finite value is the library's to refuse)
+        L.check(lib.xtrl_attn_fwd_softclamp(*args, L.ptr(alibi_slopes) if alibi_slopes is not None else None,
+                                            softclamp, L.stream()), 'attn_fwd')
         ctx.save_for_backward(q, k, v, lens, o, lse, *((mem_k, mem_v) if M else ()))
         ctx.alibi = alibi_slopes   # (no gradient: not a saved tensor of the graph)
         ctx.softclamp = softclamp
@@ -288,13 +283,7 @@ class AttentionFn(torch.autograd.Function):
         args = (L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(lens), L.ptr(o), L.ptr(lse), L.ptr(do), L.ptr(dq), L.ptr(dk),
                 L.ptr(dv), L.ptr(delta), pm(mem_k), pm(mem_v), pm(dmk), pm(dmv), pm(ws), ws_floats, b, H, k.shape[1],
                 n, dh, scale, p, seed, offset, sub, window, M, Z)
-        if ctx.softclamp != 0.:
-            L.check(lib.xtrl_attn_bwd_softclamp(*args, L.ptr(ctx.alibi) if ctx.alibi is not None else None,
-                                                ctx.softclamp, L.stream()), 'attn_bwd')
-        elif ctx.alibi is not None:
-            L.check(lib.xtrl_attn_bwd_alibi(*args, L.ptr(ctx.alibi), L.stream()), 'attn_bwd')
-        else:
-            L.check(lib.xtrl_attn_bwd_sink(*args, L.stream()), 'attn_bwd')
+        L.check(lib.xtrl_attn_bwd_softclamp(*args, pm(ctx.alibi), ctx.softclamp, L.stream()), 'attn_bwd')
         return dq, dk, dv, None, None, None, None, None, None, None, dmk, dmv, None, None, None
 
 
