@@ -1062,7 +1062,10 @@ int xtrl_sim_reset(float* state, int E, int S, uint64_t seed, uint32_t update, c
  * (xtrl_amd/fractal.py) mirrors the reference modules and their state_dict names.
  * ------------------------------------------------------------------------------------------- */
 /* attention forward on token-major q/k/v (rows b*n + i, head h at columns h*dh, one row stride);
- * causal = 0: key-padding mask only (keys j < lens[b]) */
+ * causal = 0: key-padding mask only (keys j < lens[b]); every row i < n is written, the padded ones
+ * i >= lens[b] too (they attend the lens[b] valid keys).  Precondition: lens[b] >= 1 for every b — an
+ * episode without a valid key has an empty softmax, and the forward divides 0 by 0 there (o of that
+ * episode's rows is NaN, lse -inf); the caller must not pass one. */
 int xtrl_attn_fwd_tokens(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                          const int32_t* lens, float* o, int ldo, float* lse, int b, int H, int n, int dh, float scale,
                          int causal, void* stream);

@@ -1,7 +1,8 @@
 """What the attention GPU tests share (test_gpu_parity.py, test_attn_window_gpu.py, test_attn_gqa_gpu.py,
 test_attn_sink_gpu.py, test_attn_alibi_gpu.py, test_attn_softclamp_gpu.py): the one driver of the learn-step
 attention kernels through the C ABI (attn_lib, which reaches every entry-point family: xtrl_attn_fwd / _bwd /
-_bwd_part and their _win, _gqa, _sink, _alibi and _softclamp forms), the kernel-level problem builder, the fp64
+_bwd_part and their _win, _gqa, _sink, _alibi and _softclamp forms), the driver of the token-major forward
+xtrl_attn_fwd_tokens (attn_tokens_lib; test_fractal_kernels_gpu.py), the kernel-level problem builder, the fp64
 band softmax, the one fp64 autograd wrapper over the option files' dense references (fp64_ref), the bounds
 against an fp64 reference (check_ref) and the model-level body "rollout, then n learn minibatches against a patched oracle" (rollout_and_learn).  The Learner
 builder and the other model-level bodies are test_gpu_parity's: make_learner, _packed_vs_padded,
@@ -100,6 +101,31 @@ def attn_lib(q, k, v, lens, do, scale, p, mode, abi, W=None, mem_k=None, mem_v=N
     finally:
         torch.cuda.synchronize()
         attn_lib.last = res
+    return res
+
+
+def attn_tokens_lib(buf, lens, b, H, n, dh, scale, causal=False, ldo=None, ldk=None):
+    """xtrl_attn_fwd_tokens through the C ABI, as xtrl_amd/fractal.py calls it: q, k, v are the column slices
+    [0, I), [I, 2 I), [2 I, 3 I) (I = H dh) of ``buf`` [b n][ld] on the device, o is [b n][ldo] (``ldo`` None: I)
+    and lse [b][H][n]; both hold NaN before the call, so an element the kernel did not write shows — the padding
+    columns of a wide ``ldo`` among them.  ``ldk``: a row stride for k other than q's and v's (the entry point
+    refuses it).  The call is synchronised and the result dict is left in ``attn_tokens_lib.last`` also when it
+    raises.  Returns dict(o, lse)."""
+    from xtrl_amd import _lib as L
+    I, ld = H * dh, buf.stride(0)   # noqa: E741
+    assert buf.is_cuda and buf.dtype == torch.float32 and buf.shape == (b * n, ld) and ld >= 3 * I, (buf.shape, I)
+    assert lens.is_cuda and lens.dtype == torch.int32 and lens.shape == (b,), lens
+    ldo = I if ldo is None else ldo
+    assert ldo >= I, (ldo, I)
+    res = dict(o=torch.full((b * n, ldo), float('nan'), device=DEV), lse=torch.full((b, H, n), float('nan'), device=DEV))
+    try:
+        L.check(L.lib().xtrl_attn_fwd_tokens(L.ptr(buf), ld, L.ptr(buf[:, I:]), ld if ldk is None else ldk,
+                                             L.ptr(buf[:, 2 * I:]), ld, L.ptr(lens), L.ptr(res['o']), ldo,
+                                             L.ptr(res['lse']), b, H, n, dh, scale, int(causal), L.stream()),
+                'attn_fwd_tokens')
+    finally:
+        torch.cuda.synchronize()
+        attn_tokens_lib.last = res
     return res
 
 

@@ -226,10 +226,12 @@ def test_alibi_windowed_rollout_measures_distance_after_the_pointer_shift(rows, 
     assert int(lens.max()) > 20
 
 
-def test_alibi_d256_fused_out_projection_rollout(monkeypatch):
-    """d = 256, T = 40, W = 5 with the zero key: the attention decode kernel that applies the out-projection itself."""
+@pytest.mark.parametrize('dim', [256, 384])
+def test_alibi_fused_out_projection_rollout(dim, monkeypatch):
+    """d = 256 and d = 384 (the FJ = 1 and FJ = 2 forms), T = 40, W = 5 with the zero key: the attention decode
+    kernel that applies the out-projection itself."""
     monkeypatch.setenv('XTRL_DECODE_ROWS', '0')
-    _, lens, _ = alibi_rollout_and_learn(monkeypatch, 'w5+zero', 40, 0, dim=256)
+    _, lens, _ = alibi_rollout_and_learn(monkeypatch, 'w5+zero', 40, 0, dim=dim)
     assert int(lens.max()) > 20
 
 

@@ -38,12 +38,12 @@ def gqa_ref(q, k, v, do, lens, W, keep=None):
 
 @pytest.mark.parametrize('b,H,Hkv,n,dh,W', [(3, 4, 2, 37, 16, None), (2, 4, 1, 70, 16, None), (2, 4, 2, 130, 16, None),
                                             (2, 4, 2, 130, 16, 10), (2, 4, 1, 200, 16, 64), (2, 6, 2, 64, 32, 7),
-                                            (1, 4, 2, 70, 64, None)])
+                                            (1, 4, 2, 70, 64, None), (1, 4, 2, 70, 64, 7)])
 def test_gqa_forward_and_backward_against_fp64(b, H, Hkv, n, dh, W):
     """Forward + every backward mode of the shape at p = 0 against the fp64 reference, ragged lengths
     (one full episode, one of a single step), every output NaN-filled before and finite after.  W = 10 at
-    n = 130 and W = 7 at n = 64 leave padded rows past the band: the uniform rows of k_attn_dead_fwd /
-    k_attn_dead_bwd, whose dV part sums the group's query heads."""
+    n = 130 and W = 7 at n = 64 and n = 70 leave padded rows past the band: the uniform rows of k_attn_dead_fwd /
+    k_attn_dead_bwd, whose dV part sums the group's query heads (dh = 64 at n = 70: their <64, true> forms)."""
     q, k, v, do, lens = problem(b, H, n, dh, n + dh + Hkv + (W or 0), Hkv=Hkv)
     ref = gqa_ref(q, k, v, do, lens, W)
     for mode in modes_of(n, dh):

@@ -223,10 +223,12 @@ def test_sink_packed_learn_matches_oracle(cfg, monkeypatch):
     assert learner.agent.packed_learn and len(seen) == 2
 
 
-def test_sink_d256_fused_out_projection_rollout(monkeypatch):
-    """d = 256, T = 40, M = 2 + Z: the attention decode kernel that applies the out-projection itself."""
+@pytest.mark.parametrize('dim', [256, 384])
+def test_sink_fused_out_projection_rollout(dim, monkeypatch):
+    """d = 256 and d = 384 (the FJ = 1 and FJ = 2 forms), T = 40, M = 2 + Z: the attention decode kernel that
+    applies the out-projection itself."""
     monkeypatch.setenv('XTRL_DECODE_ROWS', '0')
-    _, lens, _ = sink_rollout_and_learn(monkeypatch, 2, True, 40, 0, dim=256)
+    _, lens, _ = sink_rollout_and_learn(monkeypatch, 2, True, 40, 0, dim=dim)
     assert int(lens.max()) > 7
 
 

@@ -17,7 +17,10 @@ decode (csrc/decode.hip)
   k_decode_row<16> with two heads per wave (H = 16)          test_rollout_matches_oracle[h16x16-rows]
   k_attn_decode<32|64, 0, true>, k_decode_row<32|64, ., true> test_attn_sink_gpu.py::test_sink_rollout_and_learn_match_oracle[h4x32_gqa2_mem3+zero-*] /
                                                              [h2x64_kv1_zero-*]
-  k_embed<3> (d = 192)                                       test_rollout_matches_oracle[h3x16_d192-multi]
+  k_attn_decode<16, 2, true> (d = 384: the out-projection
+    fused with FJ = 2, with sinks)                           test_attn_sink_gpu.py::test_sink_fused_out_projection_rollout[384]
+  k_attn_decode<16, 2, true, true> (the same with ALiBi)     test_attn_alibi_gpu.py::test_alibi_fused_out_projection_rollout[384]
+  k_embed<3> (d = 192)                                      test_rollout_matches_oracle[h3x16_d192-multi]
   k_embed<8> with d = 320 (columns past d in the last group) test_rollout_matches_oracle[h4x32_d320-multi]
   k_embed<8> with d = 512                                    test_rollout_matches_oracle[h8x64_d512-multi]
   action embeddings read from memory (A > EMB_AREG = 8)      test_rollout_matches_oracle[h3x16_d192-multi] (A = 9), [h8x16_max-multi] (A = 32);
@@ -51,7 +54,10 @@ learn (csrc/train.hip)
   the learn step's sink kernels at dh = 32 / 64              test_attn_sink_gpu.py (the two configurations above)
 
 attention (csrc/attn.hip), kernel level: test_gpu_parity.py::test_attention_fwd_bwd[2-2-130-32] .. [1-2-200-64]
-(more than two key tiles at dh = 32 / 64) and test_attention_dropout_dh32_64_against_host_keep_bits."""
+(more than two key tiles at dh = 32 / 64) and test_attention_dropout_dh32_64_against_host_keep_bits;
+k_attn_dead_fwd<64, true> / k_attn_dead_bwd<64, true> (padded rows past the band at dh = 64 with Hkv < H):
+test_attn_gqa_gpu.py::test_gqa_forward_and_backward_against_fp64[1-4-2-70-64-7]; the bidirectional path of k_attn_fwd
+and the fractal forward's other kernels, one at a time: the table of test_fractal_kernels_gpu.py."""
 import numpy as np
 import pytest
 import torch

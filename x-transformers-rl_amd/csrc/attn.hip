@@ -1470,7 +1470,8 @@ extern "C" int xtrl_attn_bwd(const float* q, const float* k, const float* v, con
 }
 
 /* bidirectional / causal attention forward on token-major operands (rows b * n + i, head h at
- * columns h * dh): q, k, v with row strides ldq / ldk / ldv, out o [b * n][ldo]. */
+ * columns h * dh): q, k, v with row strides ldq / ldk / ldv, out o [b * n][ldo].
+ * Precondition: lens[b] >= 1 (no window here, so an episode without a valid key divides 0 by 0). */
 extern "C" int xtrl_attn_fwd_tokens(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                     const int32_t* lens, float* o, int ldo, float* lse, int b, int H, int n, int dh,
                                     float scale, int causal, void* stream) {
