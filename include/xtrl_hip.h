@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 29
+#define XTRL_ABI_VERSION 30
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -60,6 +60,75 @@ int xtrl_gemm_f32(const float* X, int ldx, const float* W, int ldw, const float*
  * (nn.Linear backward: dgrad = (0, 1), wgrad = (1, 1) with beta = 1 to accumulate) */
 int xtrl_gemm_ex(int trans_a, int trans_b, const float* A, int lda, const float* B, int ldb, const float* bias,
                  float* C, int ldc, int M, int N, int K, float beta, void* stream);
+
+/* The GEMM with any of its epilogues at any shape: the entry the kernel-level tests drive (tests/test_gemm_epi_gpu.py).
+ * It fills the library's internal argument block from the descriptor and takes the same dispatch as every other
+ * caller, so a shape lands on the kernel the learn step would run for it.  Epilogues (v = A . B + bias):
+ *   NONE / GELU / SILU / RELU   C = act(v) (+ R)
+ *   GELU_DROP   C = drop(gelu(v)), aux_out = drop(gelu'(v)); keep bits of xtrl_ff_dropout_mask(seed, offset, layer)
+ *   SILU_SAVE   n < act_cols: C = silu(v), aux_out = silu'(v); else C = v, aux_out = 1
+ *   MUL_AUX     C = v * aux_in            MASK_POS   C = aux_in > 0 ? v : 0
+ *   DGATE       s = sigmoid(aux_in2): C = v * s, aux_out = v * aux_in * s * (1 - s)
+ *   RES_LN      C = v + R; ln_y1 = LN(C) ln_g (+ ln_b); ln_y2 = ln_y1 + ln_b2; ln_stats[m] = (mean, rstd)
+ *   LN_BWD      C = LN_backward(v; ln_x, ln_stats, ln_g) + ln_dres; ln_part[row tile][n] = d gamma partials
+ *   LN_BWD2     g = ln_gscale v + ln_gpre; C = LN_backward(g) (ldc == N); ln_part / ln_part_b (rows of ln_pstride, 0: N);
+ *               with ln2_out the chained second LayerNorm backward of C (ln2_*)
+ * then C = beta * C + result for the element-wise epilogues.  bias[n - bias_col0] applies to n >= bias_col0.
+ * gamma: LayerNorm prologue over A's rows (A "N" only).  ln_rms: RMSNorm in the prologue and the LayerNorm
+ * epilogues.  The LayerNorm epilogues need N <= 256, N % 4 == 0, K % 4 == 0 and float4-aligned operands; their
+ * partial buffers hold ceil(M / (N <= 128 ? 128 : 64)) rows.  Unsupported combinations return XTRL_E_ARG and
+ * launch nothing. */
+#define XTRL_EPI_NONE 0
+#define XTRL_EPI_GELU 1
+#define XTRL_EPI_SILU 2
+#define XTRL_EPI_GELU_DROP 3
+#define XTRL_EPI_SILU_SAVE 4
+#define XTRL_EPI_MUL_AUX 5
+#define XTRL_EPI_DGATE 7
+#define XTRL_EPI_RELU 8
+#define XTRL_EPI_RES_LN 9
+#define XTRL_EPI_LN_BWD 10
+#define XTRL_EPI_MASK_POS 11
+#define XTRL_EPI_LN_BWD2 12
+
+typedef struct XtrlGemmDesc {
+  const float* A;
+  const float* B;
+  const float* bias;
+  const float* gamma;
+  const float* R;
+  float* C;
+  int32_t lda, ldb, ldr, ldc, M, N, K;
+  float beta;
+  int32_t bias_col0, act_cols; /* act_cols <= 0: every column */
+  const float* aux_in;
+  const float* aux_in2;
+  float* aux_out;
+  int32_t ld_aux_in, ld_aux_in2, ld_aux_out;
+  float drop_p; /* GELU_DROP: dropout probability, stream (drop_seed, drop_offset, drop_layer) */
+  uint64_t drop_seed;
+  uint32_t drop_offset, drop_layer;
+  int32_t ln_rms, ln_ld1, ln_ld2, ln_ldg, ln_pstride;
+  float ln_gscale; /* LN_BWD2 (0 is taken as given: set 1 for no scaling) */
+  const float* ln_g;
+  const float* ln_b;
+  const float* ln_b2;
+  float* ln_y1;
+  float* ln_y2;
+  float* ln_stats;
+  const float* ln_x;
+  const float* ln_dres;
+  float* ln_part;
+  const float* ln_gpre;
+  float* ln_part_b;
+  const float* ln2_g;
+  const float* ln2_x;
+  const float* ln2_stats;
+  float* ln2_out;
+  float* ln2_part;
+  float* ln2_part_b;
+} XtrlGemmDesc;
+int xtrl_gemm_epi(const XtrlGemmDesc* desc, int trans_a, int trans_b, int epi, void* stream);
 
 /* nn.Linear weight gradient: dW[N][K] = beta dW + sum_m dY[m][n] X[m][k] over M tokens.  The token
  * range is split over workgroups (partial tiles in ws, ws_floats >= splits * N * K, up to

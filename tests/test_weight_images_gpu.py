@@ -123,7 +123,10 @@ class _Step:
 def _same(a, b):
     assert a.keys() == b.keys()
     for k in a:
-        assert torch.equal(a[k], b[k]), k
+        # on the bit patterns (as test_weight_fragments_gpu): as strict on every number, and a plane the step leaves
+        # unwritten in this mode (buf.dxn) holds whatever the allocator's block held before — NaN patterns once an
+        # earlier test has filled its outputs with NaN — which never compare equal as floats
+        assert torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)), k
     assert torch.isfinite(a['grad']).all() and float(a['grad'].abs().max()) > 0.
 
 

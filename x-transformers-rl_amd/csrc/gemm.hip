@@ -2298,6 +2298,47 @@ extern "C" int xtrl_gemm_ex(int trans_a, int trans_b, const float* A, int lda, c
                        XTRL_ACT_NONE, beta, xtrl::as_stream(stream));
 }
 
+// the test-facing entry (XtrlGemmDesc): every epilogue at any shape through gemm_run's own dispatch
+static_assert(XTRL_EPI_NONE == xtrl::EPI_NONE && XTRL_EPI_GELU == xtrl::EPI_GELU && XTRL_EPI_SILU == xtrl::EPI_SILU,
+              "XTRL_EPI_* mirror GemmEpi");
+static_assert(XTRL_EPI_GELU_DROP == xtrl::EPI_GELU_DROP, "XTRL_EPI_GELU_DROP");
+static_assert(XTRL_EPI_SILU_SAVE == xtrl::EPI_SILU_SAVE, "XTRL_EPI_SILU_SAVE");
+static_assert(XTRL_EPI_MUL_AUX == xtrl::EPI_MUL_AUX, "XTRL_EPI_MUL_AUX");
+static_assert(XTRL_EPI_DGATE == xtrl::EPI_DGATE, "XTRL_EPI_DGATE");
+static_assert(XTRL_EPI_RELU == xtrl::EPI_RELU, "XTRL_EPI_RELU");
+static_assert(XTRL_EPI_RES_LN == xtrl::EPI_RES_LN, "XTRL_EPI_RES_LN");
+static_assert(XTRL_EPI_LN_BWD == xtrl::EPI_LN_BWD, "XTRL_EPI_LN_BWD");
+static_assert(XTRL_EPI_MASK_POS == xtrl::EPI_MASK_POS, "XTRL_EPI_MASK_POS");
+static_assert(XTRL_EPI_LN_BWD2 == xtrl::EPI_LN_BWD2, "XTRL_EPI_LN_BWD2");
+
+extern "C" int xtrl_gemm_epi(const XtrlGemmDesc* d, int trans_a, int trans_b, int epi, void* stream) {
+  XTRL_REQUIRE(d, "gemm_epi: null descriptor");
+  XTRL_REQUIRE(d->drop_p >= 0.f && d->drop_p < 1.f && d->drop_layer < (1u << 22), "gemm_epi: bad dropout arguments");
+  xtrl::GemmArgs g;
+  g.A = d->A; g.B = d->B; g.bias = d->bias; g.gamma = d->gamma; g.R = d->R; g.C = d->C;
+  g.lda = d->lda; g.ldb = d->ldb; g.ldr = d->ldr; g.ldc = d->ldc; g.M = d->M; g.N = d->N; g.K = d->K;
+  g.beta = d->beta;
+  g.bias_col0 = d->bias_col0;
+  if (d->act_cols > 0) g.act_cols = d->act_cols;
+  g.aux_in = d->aux_in; g.ld_aux_in = d->ld_aux_in;
+  g.aux_in2 = d->aux_in2; g.ld_aux_in2 = d->ld_aux_in2;
+  g.aux_out = d->aux_out; g.ld_aux_out = d->ld_aux_out;
+  if (epi == xtrl::EPI_GELU_DROP && d->drop_p > 0.f) {   // as linear_fwd (train.hip)
+    g.seed = d->drop_seed; g.drop_off = d->drop_offset; g.drop_layer = d->drop_layer;
+    g.drop_thresh = xtrl::dropout_thresh(d->drop_p);
+    g.drop_thresh8 = xtrl::dropout_thresh8(d->drop_p);
+    g.inv_keep = 1.f / (1.f - d->drop_p);
+  }
+  g.ln_g = d->ln_g; g.ln_rms = d->ln_rms; g.ln_b = d->ln_b; g.ln_b2 = d->ln_b2;
+  g.ln_y1 = d->ln_y1; g.ln_ld1 = d->ln_ld1; g.ln_y2 = d->ln_y2; g.ln_ld2 = d->ln_ld2;
+  g.ln_stats = d->ln_stats; g.ln_x = d->ln_x; g.ln_dres = d->ln_dres; g.ln_part = d->ln_part;
+  g.ln_gpre = d->ln_gpre; g.ln_ldg = d->ln_ldg; g.ln_gscale = d->ln_gscale; g.ln_part_b = d->ln_part_b;
+  g.ln_pstride = d->ln_pstride;
+  g.ln2_g = d->ln2_g; g.ln2_x = d->ln2_x; g.ln2_stats = d->ln2_stats; g.ln2_out = d->ln2_out;
+  g.ln2_part = d->ln2_part; g.ln2_part_b = d->ln2_part_b;
+  return xtrl::gemm_run(g, trans_a, trans_b, epi, xtrl::as_stream(stream));
+}
+
 extern "C" int xtrl_gemm_wgrad(const float* dY, int ldy, const float* X, int ldx, float* dW, int ldw, int M, int N,
                                int K, float beta, float* ws, int64_t ws_floats, void* stream) {
   return xtrl::gemm_wgrad(dY, ldy, X, ldx, dW, ldw, M, N, K, beta, ws, ws_floats, xtrl::as_stream(stream), nullptr, 0);

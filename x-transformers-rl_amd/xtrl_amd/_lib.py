@@ -13,7 +13,7 @@ from pathlib import Path
 import torch   # noqa: F401  (load torch's HIP runtime first so the library binds to the same one)
 
 LIB_PATH = Path(os.environ.get('XTRL_LIB', Path(__file__).resolve().parent / 'libxtrl_hip.so'))   # override: A/B experiments
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 P = C.c_void_p
 I32, I64, U32, U64, F32 = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
@@ -154,6 +154,26 @@ class FractalTrainDesc(C.Structure):
                 + [('level', C.POINTER(FractalTrainLevel))])
 
 
+# GemmEpi values (XTRL_EPI_*)
+EPI_NONE, EPI_GELU, EPI_SILU, EPI_GELU_DROP, EPI_SILU_SAVE, EPI_MUL_AUX = 0, 1, 2, 3, 4, 5
+EPI_DGATE, EPI_RELU, EPI_RES_LN, EPI_LN_BWD, EPI_MASK_POS, EPI_LN_BWD2 = 7, 8, 9, 10, 11, 12
+
+
+class GemmDesc(C.Structure):
+    """One GEMM with any epilogue (XtrlGemmDesc, xtrl_gemm_epi): the kernel-level tests' entry."""
+    _fields_ = ([(n, P) for n in ('A', 'B', 'bias', 'gamma', 'R', 'C')]
+                + [(n, I32) for n in ('lda', 'ldb', 'ldr', 'ldc', 'M', 'N', 'K')]
+                + [('beta', F32), ('bias_col0', I32), ('act_cols', I32)]
+                + [(n, P) for n in ('aux_in', 'aux_in2', 'aux_out')]
+                + [(n, I32) for n in ('ld_aux_in', 'ld_aux_in2', 'ld_aux_out')]
+                + [('drop_p', F32), ('drop_seed', U64), ('drop_offset', U32), ('drop_layer', U32)]
+                + [(n, I32) for n in ('ln_rms', 'ln_ld1', 'ln_ld2', 'ln_ldg', 'ln_pstride')]
+                + [('ln_gscale', F32)]
+                + [(n, P) for n in ('ln_g', 'ln_b', 'ln_b2', 'ln_y1', 'ln_y2', 'ln_stats', 'ln_x', 'ln_dres', 'ln_part',
+                                    'ln_gpre', 'ln_part_b', 'ln2_g', 'ln2_x', 'ln2_stats', 'ln2_out', 'ln2_part',
+                                    'ln2_part_b')])
+
+
 class BatchDesc(C.Structure):
     _fields_ = ([(n, I32) for n in ('N', 'Tmax', 'n', 'b', 'S', 'A', 'B', 'continuous')]
                 + [(n, P) for n in ('states', 'actions', 'actions_f', 'rewards', 'logp', 'bounds', 'values', 'returns',
@@ -168,6 +188,7 @@ SIGNATURES = {
     'xtrl_last_error': (C.c_char_p, []),
     'xtrl_gemm_f32': (I32, [P, I32, P, I32, P, P, P, I32, P, I32, P, I64, I32, I32, I32, I32, P]),
     'xtrl_gemm_ex': (I32, [I32, I32, P, I32, P, I32, P, P, I32, I32, I32, I32, F32, P]),
+    'xtrl_gemm_epi': (I32, [C.POINTER(GemmDesc), I32, I32, I32, P]),
     'xtrl_gemm_wgrad': (I32, [P, I32, P, I32, P, I32, I32, I32, I32, F32, P, I64, P]),
     'xtrl_gemm_wgrad_db': (I32, [P, I32, P, I32, P, I32, I32, I32, I32, F32, P, I64, P, I32, P]),
     'xtrl_linear_gelu_drop': (I32, [P, I32, P, P, P, I32, P, I32, I32, I32, I32, F32, U64, U32, U32, P]),
@@ -262,7 +283,8 @@ STRUCTS = {'XtrlDecodeLayer': DecodeLayer, 'XtrlRngState': RngState, 'XtrlDecode
            'XtrlTrainLayer': TrainLayer, 'XtrlTrainDesc': TrainDesc, 'XtrlBatchDesc': BatchDesc,
            'XtrlLossDesc': LossDesc, 'XtrlFractalLevel': FractalLevel, 'XtrlFractalDesc': FractalDesc,
            'XtrlFractalTrainLevel': FractalTrainLevel, 'XtrlFractalTrainDesc': FractalTrainDesc,
-           'XtrlWimgEntry': WimgEntry, 'XtrlWfragEntry': WfragEntry}
+           'XtrlWimgEntry': WimgEntry, 'XtrlWfragEntry': WfragEntry,
+           'XtrlGemmDesc': GemmDesc}
 
 _lib = None
 
