@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 30
+#define XTRL_ABI_VERSION 31
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -996,6 +996,76 @@ int xtrl_glu_drop_fwd(const float* u, int ldu, float* h, int ldh, int M, int ff,
                       uint32_t offset, uint32_t layer, void* stream);
 int xtrl_glu_drop_bwd(const float* dh, int lddh, const float* u, int ldu, float* du, int lddu, int M, int ff, float p,
                       uint64_t seed, uint32_t offset, uint32_t layer, void* stream);
+/* The learn step's row kernels one launch at a time: the entry the kernel-level tests drive
+ * (tests/test_learn_rows_gpu.py).  `op` names a launcher of csrc/train.hip — the function the learn steps call,
+ * not a copy — and the descriptor's slots carry its operands (in[] read-only, out[] written, ld[] row strides,
+ * n[] sizes and flags, f[] scalars; float unless noted, i32 = int32_t).  `part` / `part_floats` is the
+ * partial-sum workspace (XtrlTrainDesc.part) of the ops that reduce over rows.  Argument errors (NULL descriptor,
+ * unknown op, d > 512, dh not 16 / 32 / 64, a workspace too small, ...) return XTRL_E_ARG and launch nothing.
+ *   EMBED         in: swr, w_pin, act_emb, act_emb_b, reward_embed, w_se, b_se, lat_e, prev_af, next_af,
+ *                 prev_a i32, next_a i32, ln_g, rows i32 (packed rows or NULL); out: x0 [T][d], ac_in [T][in_dim],
+ *                 ewa [T][2d], xn [T][d], st [T][2]; n: T, n, S, A, d, in_dim, continuous, evolutionary, rms,
+ *                 ln (1: k_embed_ln, d <= 256; 0: k_embed); f: keep
+ *   LATENT_EMBED  in: latent [b][G], w [d][G], bias; out: lat_e [b][d]; n: b, G, d
+ *   LN_FWD        in: x [T][d], gamma; out: y1, y2 (or NULL), stats [T][2]; ld: ld1, ld2; n: T, d, rms
+ *   LN_BWD        in: g1, g2 (or NULL), x, stats, gamma, dres (or NULL; may alias dx); out: dx [T][d], dgamma,
+ *                 dbeta (NULL, or dgamma + d); ld: ldg1, ldg2; n: T, d, rms; f: s1; part
+ *   QKV_PREP      in: proj [T][n_qkv], vfirst, inv_freq, rows i32 (packed) or NULL; out: qkv [T][I + 2 Ikv];
+ *                 ld: n_qkv, ld_vfirst; n: T, n, b, H, Hkv, dh, rot_dim, mix_col (< 0: none), qk_norm; f: xpos_base
+ *   QKV_PREP_BWD  as QKV_PREP with out: dproj (in place), dvfirst [T][Ikv]; n[9] first_layer, n[10] accumulate
+ *   COLSUM        in: src, rw (or NULL); out: dst (accumulated); ld: ld, ld_rw; n: rows, cols; f: rw_scale; part
+ *   COLSUM_FINAL  in: part [chunks][cols]; out: dst (accumulated); n: chunks, cols
+ *   COLSUM_QUEUE  jobs[n_jobs] (a host array): each job's partials are copied into the plane the deferred
+ *                 column-sum queue hands out over part / part_floats (flushing when its 16 slots or the
+ *                 workspace are full), then the queue is flushed
+ *   EMBED_GRAD    in: g1, prev i32 (both NULL: next only), g2, next i32; out: dst [A][d] (accumulated);
+ *                 ld: ld1, ld2; n: T, d, A; part
+ *   LATENT_GRAD   in: dac, ep_off i32 (packed) or NULL, latent [b][G]; out: dw [d][G], db [d] (accumulated);
+ *                 ld: ld; n: off, b, n, d, G; part (holds dlat [b][d] afterwards)
+ *   VALID_ROWS    in: lens i32 [b]; out: vrows i32 [Tv], vinv i32 [b n], ep_off i32 [b + 1] (or NULL); n: b, n, Tv
+ *   GATHER / SCATTER  in: src, rows / inv i32; out: dst; ld: lds, ldd; n: rows (gather: listed, scatter: T), cols
+ *   CAUSAL_MEAN   in: src, add (or NULL); out: dst; ld: lds, ldadd, ldd; n: b, n, d, rev
+ *   AXPB          in: a (lda = 0: one row broadcast), b (or NULL); out: dst; ld: lda, ldb, ldd; n: rows, cols; f: alpha
+ *   ACTION_ROWS   in: act i32, W [A][d]; out: out; ld: ldo; n: rows, d, A
+ *   BCAST_EP      in: src [rows / n][d]; out: dst; ld: ldd; n: rows, n, d */
+#define XTRL_ROWS_EMBED 0
+#define XTRL_ROWS_LATENT_EMBED 1
+#define XTRL_ROWS_LN_FWD 2
+#define XTRL_ROWS_LN_BWD 3
+#define XTRL_ROWS_QKV_PREP 4
+#define XTRL_ROWS_QKV_PREP_BWD 5
+#define XTRL_ROWS_COLSUM 6
+#define XTRL_ROWS_COLSUM_FINAL 7
+#define XTRL_ROWS_COLSUM_QUEUE 8
+#define XTRL_ROWS_EMBED_GRAD 9
+#define XTRL_ROWS_LATENT_GRAD 10
+#define XTRL_ROWS_VALID_ROWS 11
+#define XTRL_ROWS_GATHER 12
+#define XTRL_ROWS_SCATTER 13
+#define XTRL_ROWS_CAUSAL_MEAN 14
+#define XTRL_ROWS_AXPB 15
+#define XTRL_ROWS_ACTION_ROWS 16
+#define XTRL_ROWS_BCAST_EP 17
+
+typedef struct XtrlColsumJob {
+  const float* part; /* [chunks][cols] partials (device) */
+  float* dst;        /* [cols], accumulated */
+  int32_t chunks, cols;
+} XtrlColsumJob;
+
+typedef struct XtrlRowsDesc {
+  const void* in[16];
+  void* out[6];
+  int32_t ld[4];
+  int32_t n[12];
+  float f[2];
+  float* part;
+  int64_t part_floats;
+  const XtrlColsumJob* jobs;
+  int32_t n_jobs;
+} XtrlRowsDesc;
+int xtrl_learn_rows(const XtrlRowsDesc* desc, int op, void* stream);
+
 /* floats of XtrlTrainDesc.part (the partial-sum workspace) a learn step of T = b * n tokens needs;
  * host-only, no device call */
 int64_t xtrl_train_part_floats(int T, int b, int d, int A);

@@ -48,7 +48,8 @@ extern "C" int64_t xtrl_struct_size(const char* name) {
                {"XtrlLossDesc", sizeof(XtrlLossDesc)},       {"XtrlFractalLevel", sizeof(XtrlFractalLevel)},
                {"XtrlFractalDesc", sizeof(XtrlFractalDesc)},     {"XtrlFractalTrainLevel", sizeof(XtrlFractalTrainLevel)},
                {"XtrlFractalTrainDesc", sizeof(XtrlFractalTrainDesc)}, {"XtrlWimgEntry", sizeof(XtrlWimgEntry)},
-               {"XtrlWfragEntry", sizeof(XtrlWfragEntry)},           {"XtrlGemmDesc", sizeof(XtrlGemmDesc)}};
+               {"XtrlWfragEntry", sizeof(XtrlWfragEntry)},           {"XtrlGemmDesc", sizeof(XtrlGemmDesc)},
+               {"XtrlRowsDesc", sizeof(XtrlRowsDesc)},               {"XtrlColsumJob", sizeof(XtrlColsumJob)}};
   for (const auto& s : sizes)
     if (name && strcmp(name, s.name) == 0) return s.size;
   return -1;

@@ -895,6 +895,53 @@ __global__ void k_rows_bcast_ep(const float* src, float* dst, int ldd, int rows,
 // ---- host helpers -----------------------------------------------------------------------------
 inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
+// ---- launchers of the row kernels: one function per launch, called by the learn steps below and by
+// the kernel-level test entry (xtrl_learn_rows) — the tests run these launches, not copies of them
+void colsum_final(const float* part, int chunks, int cols, float* dst, hipStream_t s) {
+  hipLaunchKernelGGL(k_colsum_final, dim3(blocks(cols, CS_COLS)), dim3(64 * CS_WAVES), 0, s, part, chunks, cols, dst);
+}
+// the embeddings of ea.T tokens; ln: with layer 0's attention pre-norm folded in (k_embed_ln, d <= 256)
+void embed_rows(const EmbedArgs& ea, bool ln, hipStream_t s) {
+  if (ln) {
+    if (ea.S == 8) hipLaunchKernelGGL(k_embed_ln<8>, dim3(blocks(ea.T, EMB_LN_TOK)), dim3(256), 0, s, ea);
+    else hipLaunchKernelGGL(k_embed_ln<0>, dim3(blocks(ea.T, EMB_LN_TOK)), dim3(256), 0, s, ea);
+  } else if (ea.S == 8) {
+    hipLaunchKernelGGL(k_embed<8>, dim3(blocks(ea.T, EMB_TOK)), dim3(256), 0, s, ea);
+  } else {
+    hipLaunchKernelGGL(k_embed<0>, dim3(blocks(ea.T, EMB_TOK)), dim3(256), 0, s, ea);
+  }
+}
+void latent_embed(const float* latent, const float* w, const float* bias, float* out, int b, int G, int d,
+                  hipStream_t s) {
+  hipLaunchKernelGGL(k_latent_embed, dim3(blocks(b * d, 256)), dim3(256), 0, s, latent, w, bias, out, b, G, d);
+}
+// rotary / qk norm / value mix of a layer's projection rows and its backward: padded form (b episodes of
+// a.n steps, token and position from the grid) or packed (a.rows: a.T listed rows)
+void qkv_prep(const PrepArgs& a, int b, hipStream_t s) {
+  const unsigned pb = blocks((a.I + 2 * a.Ikv) / 2, PREP_T);
+  hipLaunchKernelGGL(k_qkv_prep, a.rows ? dim3(pb, a.T) : dim3(pb, a.n, b), dim3(PREP_T), 0, s, a);
+}
+void qkv_prep_bwd(const PrepBwdArgs& a, int b, hipStream_t s) {
+  const unsigned pb = blocks((a.I + 2 * a.Ikv) / 2, PREP_T);
+  hipLaunchKernelGGL(k_qkv_prep_bwd, a.rows ? dim3(pb, a.T) : dim3(pb, a.n, b), dim3(PREP_T), 0, s, a);
+}
+// the gene conditioning's gradients from dac[:, off : off + d]: the per-episode sums into part [b][d], then
+// dw [d][G] and db [d] accumulated
+int latent_grads(const float* dac, int ld, int off, int b, int n, int d, int G, const int32_t* ep_off,
+                 const float* latent, float* part, int64_t part_floats, float* dw, float* db, hipStream_t s) {
+  XTRL_REQUIRE((int64_t)b * d <= part_floats, "train: partial-sum workspace too small");
+  hipLaunchKernelGGL(k_latent_grad, dim3(b, (d + 63) / 64), dim3(64 * LG_G), 0, s, dac, ld, off, b, n, d, part, ep_off);
+  hipLaunchKernelGGL(k_latent_wgrad, dim3(blocks(d * (G + 1), 256)), dim3(256), 0, s, part, latent, b, d, G, dw, db);
+  XTRL_LAUNCHED("train latent grad");
+  return XTRL_OK;
+}
+void action_rows(const int32_t* act, const float* W, int A, float* out, int ldo, int rows, int d, hipStream_t s) {
+  hipLaunchKernelGGL(k_action_rows, dim3(blocks((int64_t)rows * d, 256)), dim3(256), 0, s, act, W, A, out, ldo, rows, d);
+}
+void rows_bcast_ep(const float* src, float* dst, int ldd, int rows, int n, int d, hipStream_t s) {
+  hipLaunchKernelGGL(k_rows_bcast_ep, dim3(blocks((int64_t)rows * d, 256)), dim3(256), 0, s, src, dst, ldd, rows, n, d);
+}
+
 struct Ctx {
   const XtrlTrainDesc* D;
   hipStream_t s;
@@ -1045,8 +1092,39 @@ int colsum(const Ctx& c, const float* src, int ld, int rows, int cols, float* ds
   XTRL_REQUIRE((int64_t)chunks * cols <= c.D->part_floats, "train: partial-sum workspace too small");
   hipLaunchKernelGGL(k_colsum_part, dim3(blocks(cols, 256), chunks), dim3(256), 0, c.s, src, ld, rows, cols,
                      chunk_rows, rw, ld_rw, rw_scale, c.D->part);
-  hipLaunchKernelGGL(k_colsum_final, dim3(blocks(cols, CS_COLS)), dim3(64 * CS_WAVES), 0, c.s, c.D->part, chunks, cols, dst);
+  colsum_final(c.D->part, chunks, cols, dst, c.s);
   XTRL_LAUNCHED("train colsum");
+  return XTRL_OK;
+}
+
+// discrete action-embedding gradient (k_embed_grad_part's operands; no prev: nullptr, 0, nullptr)
+// into dst [A][d]: 16-row partials (loads in flight), as many as the partial workspace holds.
+// what ("train" / "fractal train") prefixes the error texts.
+int embed_grad(const Ctx& c, const char* what, const float* g1, int ld1, const int32_t* prev, const float* g2, int ld2,
+               const int32_t* next, float* dst) {
+  const XtrlTrainDesc* D = c.D;
+  const int T = c.T, d = D->d, A = D->A;
+  const hipStream_t s = c.s;
+  int chunks = (int)std::min<int64_t>(std::min(1024, std::max(1, T / 16)),
+                                      std::max<int64_t>(1, D->part_floats / ((int64_t)A * d)));
+  const int chunk_rows = (T + chunks - 1) / chunks;
+  chunks = (T + chunk_rows - 1) / chunk_rows;
+  XTRL_REQUIRE((int64_t)chunks * A * d <= D->part_floats, "%s: partial-sum workspace too small", what);
+  const dim3 eg(blocks(d, 256), chunks);
+  if (A <= 4)
+    hipLaunchKernelGGL(k_embed_grad_part<4>, eg, dim3(256), 0, s, g1, ld1, prev, g2, ld2, next, T, d, A, chunk_rows,
+                       D->part);
+  else if (A <= 8)
+    hipLaunchKernelGGL(k_embed_grad_part<8>, eg, dim3(256), 0, s, g1, ld1, prev, g2, ld2, next, T, d, A, chunk_rows,
+                       D->part);
+  else
+    hipLaunchKernelGGL(k_embed_grad_part<EMB_MAXA>, eg, dim3(256), 0, s, g1, ld1, prev, g2, ld2, next, T, d, A,
+                       chunk_rows, D->part);
+  colsum_final(D->part, chunks, A * d, dst, s);
+  if (const hipError_t e = hipGetLastError()) {
+    set_error("%s embed grad: %s", what, hipGetErrorString(e));
+    return XTRL_E_HIP;
+  }
   return XTRL_OK;
 }
 
@@ -1088,35 +1166,6 @@ struct Backward {
       return XTRL_E_HIP;
     }
     ++bucket;
-    return XTRL_OK;
-  }
-  // discrete action-embedding gradient (k_embed_grad_part's operands; no prev: nullptr, 0, nullptr)
-  // into dst [A][d]: 16-row partials (loads in flight), as many as the partial workspace holds
-  int embed_grad(const float* g1, int ld1, const int32_t* prev, const float* g2, int ld2, const int32_t* next,
-                 float* dst) {
-    const int T = c.T, d = D->d, A = D->A;
-    const hipStream_t s = c.s;
-    int chunks = (int)std::min<int64_t>(std::min(1024, std::max(1, T / 16)),
-                                        std::max<int64_t>(1, D->part_floats / ((int64_t)A * d)));
-    const int chunk_rows = (T + chunks - 1) / chunks;
-    chunks = (T + chunk_rows - 1) / chunk_rows;
-    XTRL_REQUIRE((int64_t)chunks * A * d <= D->part_floats, "%s: partial-sum workspace too small", what);
-    const dim3 eg(blocks(d, 256), chunks);
-    if (A <= 4)
-      hipLaunchKernelGGL(k_embed_grad_part<4>, eg, dim3(256), 0, s, g1, ld1, prev, g2, ld2, next, T, d, A, chunk_rows,
-                         D->part);
-    else if (A <= 8)
-      hipLaunchKernelGGL(k_embed_grad_part<8>, eg, dim3(256), 0, s, g1, ld1, prev, g2, ld2, next, T, d, A, chunk_rows,
-                         D->part);
-    else
-      hipLaunchKernelGGL(k_embed_grad_part<EMB_MAXA>, eg, dim3(256), 0, s, g1, ld1, prev, g2, ld2, next, T, d, A,
-                         chunk_rows, D->part);
-    hipLaunchKernelGGL(k_colsum_final, dim3(blocks(A * d, CS_COLS)), dim3(64 * CS_WAVES), 0, s, D->part, chunks, A * d,
-                       dst);
-    if (const hipError_t e = hipGetLastError()) {
-      set_error("%s embed grad: %s", what, hipGetErrorString(e));
-      return XTRL_E_HIP;
-    }
     return XTRL_OK;
   }
   // the input projection's weight gradient from dY [T][d] (+ its bias gradient db), last of the
@@ -1161,6 +1210,7 @@ int ln_bwd(const Ctx& c, const float* g1, int ldg1, float s1, const float* g2, i
            const float* st, const float* gamma, const float* dres, float* dx, float* dgamma, float* dbeta = nullptr) {
   const int d = c.D->d, nb = (int)blocks(c.T, LN_ROWS);
   XTRL_REQUIRE((int64_t)nb * d * (dbeta ? 2 : 1) <= c.D->part_floats, "train: partial-sum workspace too small");
+  XTRL_REQUIRE(!dbeta || dbeta == dgamma + d, "train: LayerNorm weight and bias gradients must be adjacent");
   // with d beta: the two partial rows of a block side by side ([gamma | beta], stride 2d), so one
   // column-sum launch finishes both when the parameters are adjacent (nn.LayerNorm weight, bias)
   const int ps = dbeta ? 2 * d : d;
@@ -1171,13 +1221,7 @@ int ln_bwd(const Ctx& c, const float* g1, int ldg1, float s1, const float* g2, i
   else if (d <= 128) hipLaunchKernelGGL(k_ln_bwd<2>, g, bl, 0, c.s, g1, ldg1, s1, g2, ldg2, x, st, gamma, dres, dx, P, pb, ps, c.T, d, c.D->rms_norm);
   else if (d <= 256) hipLaunchKernelGGL(k_ln_bwd<4>, g, bl, 0, c.s, g1, ldg1, s1, g2, ldg2, x, st, gamma, dres, dx, P, pb, ps, c.T, d, c.D->rms_norm);
   else hipLaunchKernelGGL(k_ln_bwd<8>, g, bl, 0, c.s, g1, ldg1, s1, g2, ldg2, x, st, gamma, dres, dx, P, pb, ps, c.T, d, c.D->rms_norm);
-  if (!dbeta) {
-    hipLaunchKernelGGL(k_colsum_final, dim3(blocks(d, CS_COLS)), dim3(64 * CS_WAVES), 0, c.s, P, nb, d, dgamma);
-  } else if (dbeta == dgamma + d) {
-    hipLaunchKernelGGL(k_colsum_final, dim3(blocks(2 * d, CS_COLS)), dim3(64 * CS_WAVES), 0, c.s, P, nb, 2 * d, dgamma);
-  } else {
-    XTRL_REQUIRE(false, "train: LayerNorm weight and bias gradients must be adjacent");
-  }
+  colsum_final(P, nb, dbeta ? 2 * d : d, dgamma, c.s);
   XTRL_LAUNCHED("train ln_bwd");
   return XTRL_OK;
 }
@@ -1218,8 +1262,7 @@ int dgrad_ln_bwd(const Ctx& c, const float* dY, int ldy, const float* W, int N, 
   g.ln_rms = c.D->rms_norm;
   c.img(g, 1, EPI_LN_BWD);
   if ((rc = gemm_run(g, 0, 1, EPI_LN_BWD, c.s))) return rc;
-  if (!P)
-    hipLaunchKernelGGL(k_colsum_final, dim3(blocks(d, CS_COLS)), dim3(64 * CS_WAVES), 0, c.s, c.D->part, nb, d, dgamma);
+  if (!P) colsum_final(c.D->part, nb, d, dgamma, c.s);
   XTRL_LAUNCHED("train dgrad_ln_bwd");
   return XTRL_OK;
 }
@@ -1363,6 +1406,10 @@ __global__ void k_scatter_rows(const float* src, int lds, const int32_t* inv, in
   else
     *dp = j >= 0 ? src[(int64_t)j * lds + c] : 0.f;
 }
+void valid_rows(const int32_t* lens, int b, int n, int Tv, int32_t* vrows, int32_t* vinv, int32_t* ep_off,
+                hipStream_t s) {
+  hipLaunchKernelGGL(k_valid_rows, dim3(1), dim3(1024), 0, s, lens, b, n, Tv, vrows, vinv, ep_off);
+}
 bool vec4_ok(const float* a, int lda, const float* b, int ldb, int cols) {
   return cols % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)b % 16) == 0;
 }
@@ -1398,7 +1445,7 @@ int heads_forward(const Ctx& c) {
     // world-model heads over the Tv valid rows: their outputs feed only masked losses (xtrl.py:944,
     // 949), the padded rows' pred / done are stored as zeros
     const int Tv = D->Tv;
-    hipLaunchKernelGGL(k_valid_rows, dim3(1), dim3(1024), 0, s, D->lens, D->b, D->n, D->Tv, D->vrows, D->vinv);
+    valid_rows(D->lens, D->b, D->n, D->Tv, D->vrows, D->vinv, nullptr, s);
     gather_rows(D->ewa, 2 * d, D->vrows, Tv, 2 * d, D->ewa_v, 2 * d, s);
     if ((rc = linear_fwd(c, D->ewa_v, 2 * d, c.P(D->w_pd), c.P(D->b_pd), D->hp_v, ldp, Tv, d + 1, 2 * d, EPI_SILU_SAVE,
                          nullptr, D->zp_v, ldp, d)))
@@ -1468,12 +1515,9 @@ int heads_backward(const Ctx& c, const Ctx& cw, Fork& F, bool embed_cols = true)
   if ((rc = F.fork())) return rc;
   if ((rc = wgrad(cw, D->dac + d, D->in_dim, D->swr, D->S + 1, c.G(D->w_se), T, d, D->S, c.G(D->b_se)))) return rc;
   if (D->evolutionary) {
-    XTRL_REQUIRE((int64_t)D->b * d <= D->part_floats, "train: partial-sum workspace too small");
-    hipLaunchKernelGGL(k_latent_grad, dim3(D->b, (d + 63) / 64), dim3(64 * LG_G), 0, s, D->dac, D->in_dim, 2 * d,
-                       D->b, D->n, d, D->part, D->packed ? D->ep_off : nullptr);
-    hipLaunchKernelGGL(k_latent_wgrad, dim3(blocks(d * (D->G + 1), 256)), dim3(256), 0, s, D->part, D->latent, D->b,
-                       d, D->G, c.G(D->w_lat), c.G(D->b_lat));
-    XTRL_LAUNCHED("train latent grad");
+    if ((rc = latent_grads(D->dac, D->in_dim, 2 * d, D->b, D->n, d, D->G, D->packed ? D->ep_off : nullptr, D->latent,
+                           D->part, D->part_floats, c.G(D->w_lat), c.G(D->b_lat), s)))
+      return rc;
   }
   // ---- world-model heads
   if (cmp) {   // on the Tv valid rows; dewa's padded rows are zero (their dzp rows were)
@@ -1514,10 +1558,7 @@ int train_forward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
   if (D->wfrag && D->wfrag_tab && D->wfrag_tab_host && D->wfrag_n > 0)
     if ((rc = wfrag_build(D->flat, D->wfrag_tab_host, D->wfrag_tab, D->wfrag_n, D->wfrag, D->wfrag_bytes, s))) return rc;
   // embeddings
-  if (D->evolutionary) {
-    hipLaunchKernelGGL(k_latent_embed, dim3(blocks(D->b * d, 256)), dim3(256), 0, s, D->latent, c.P(D->w_lat),
-                       c.P(D->b_lat), D->lat_e, D->b, D->G, d);
-  }
+  if (D->evolutionary) latent_embed(D->latent, c.P(D->w_lat), c.P(D->b_lat), D->lat_e, D->b, D->G, d, s);
   EmbedArgs ea{D->swr, c.P(D->w_pin), c.P(D->act_emb), c.P(D->act_emb_b), c.P(D->reward_embed), c.P(D->w_se),
                c.P(D->b_se), D->lat_e, D->prev_action_f, D->next_action_f, D->prev_action, D->next_action,
                D->layers[0].x_attn, D->ac_in, D->ewa, T, D->n, D->S, D->A, d, D->in_dim, D->continuous,
@@ -1531,13 +1572,8 @@ int train_forward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     ea.ln_g = c.P(L0.ln_attn);
     ea.xn = L0.xn_attn;
     ea.st = L0.st_attn;
-    if (D->S == 8) hipLaunchKernelGGL(k_embed_ln<8>, dim3(blocks(T, EMB_LN_TOK)), dim3(256), 0, s, ea);
-    else hipLaunchKernelGGL(k_embed_ln<0>, dim3(blocks(T, EMB_LN_TOK)), dim3(256), 0, s, ea);
-  } else if (D->S == 8) {
-    hipLaunchKernelGGL(k_embed<8>, dim3(blocks(T, EMB_TOK)), dim3(256), 0, s, ea);
-  } else {
-    hipLaunchKernelGGL(k_embed<0>, dim3(blocks(T, EMB_TOK)), dim3(256), 0, s, ea);
   }
+  embed_rows(ea, fuse, s);
   XTRL_LAUNCHED("train embed");
   for (int li = 0; li < D->L; ++li) {
     const XtrlTrainLayer& Ly = D->layers[li];
@@ -1549,8 +1585,7 @@ int train_forward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     const int mix_col = Ly.mix ? nq3 + (D->gate_values ? I : 0) : -1;
     PrepArgs pa{Ly.proj, D->layers[0].proj, Ly.qkv, D->inv_freq, T, D->n, D->H, D->dh, I, Ly.n_qkv,
                 D->layers[0].n_qkv, D->rot_dim, mix_col, D->qk_norm, D->xpos_base, rows, Ikv};
-    const dim3 pg = rows ? dim3(blocks(nq3 / 2, PREP_T), T) : dim3(blocks(nq3 / 2, PREP_T), D->n, D->b);
-    hipLaunchKernelGGL(k_qkv_prep, pg, dim3(PREP_T), 0, s, pa);
+    qkv_prep(pa, D->b, s);
     XTRL_LAUNCHED("train qkv_prep");
     const AttnProblem ap = attn_problem(c, Ly, li);
     if ((rc = attn_fwd_ex(ap, Ly.qkv, Ly.qkv + I, Ly.qkv + I + Ikv, Ly.o, Ly.lse,
@@ -1644,9 +1679,7 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     g.ln_gpre = D->dewa; g.ln_ldg = 2 * d; g.ln_gscale = D->frac_head_grad; g.ln_part = P ? P : D->part;
     c.img(g, 1, EPI_LN_BWD2);
     if ((rc = gemm_run(g, 0, 1, EPI_LN_BWD2, s))) return rc;
-    if (!P)
-      hipLaunchKernelGGL(k_colsum_final, dim3(blocks(d, CS_COLS)), dim3(64 * CS_WAVES), 0, s, D->part, nb, d,
-                         c.G(D->ln_final));
+    if (!P) colsum_final(D->part, nb, d, c.G(D->ln_final), s);
     XTRL_LAUNCHED("train final-norm backward");
   } else if ((rc = ln_bwd(c, D->dac, D->in_dim, D->frac_head_grad, D->dewa, 2 * d, D->x_final, D->st_final,
                           c.P(D->ln_final), nullptr, dx_top, c.G(D->ln_final)))) {
@@ -1730,8 +1763,7 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     PrepBwdArgs pb{dproj, Ly.proj, D->layers[0].proj, D->dvfirst, D->inv_freq, T, D->n, D->H, D->dh, I,
                    Ly.n_qkv, D->layers[0].n_qkv, D->rot_dim, mix_col, li == 0 ? 1 : 0,
                    (li == 0 ? any_mix : deeper_mix) ? 1 : 0, D->qk_norm, D->xpos_base, rows, Ikv};
-    const dim3 pg = rows ? dim3(blocks(nq3 / 2, PREP_T), T) : dim3(blocks(nq3 / 2, PREP_T), D->n, D->b);
-    hipLaunchKernelGGL(k_qkv_prep_bwd, pg, dim3(PREP_T), 0, s, pb);
+    qkv_prep_bwd(pb, D->b, s);
     XTRL_LAUNCHED("train qkv_prep_bwd");
     // q | k | v | gate | mix projection
     if ((rc = F.fork())) return rc;
@@ -1761,7 +1793,8 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     if ((rc = wgrad(cw, D->dewa + d, 2 * d, D->next_action_f, D->A, c.G(D->act_emb), T, d, D->A))) return rc;
     if ((rc = colsum(c, D->dx, d, T, d, c.G(D->act_emb_b)))) return rc;
     if ((rc = colsum(c, D->dewa + d, 2 * d, T, d, c.G(D->act_emb_b)))) return rc;
-  } else if ((rc = B.embed_grad(D->dx, d, D->prev_action, D->dewa + d, 2 * d, D->next_action, c.G(D->act_emb)))) {
+  } else if ((rc = embed_grad(c, B.what, D->dx, d, D->prev_action, D->dewa + d, 2 * d, D->next_action,
+                              c.G(D->act_emb)))) {
     return rc;
   }
   return B.finish();
@@ -1824,7 +1857,7 @@ int train_forward(const XtrlTrainDesc* D, hipStream_t s) {
   PackBufs B;
   if (int rc = packed_view(D, P, B)) return rc;
   const int T = D->b * D->n, Tv = D->Tv, S1 = D->S + 1, A = D->continuous ? D->A : 1;
-  hipLaunchKernelGGL(k_valid_rows, dim3(1), dim3(1024), 0, s, D->lens, D->b, D->n, Tv, D->vrows, D->vinv, D->ep_off);
+  valid_rows(D->lens, D->b, D->n, Tv, D->vrows, D->vinv, D->ep_off, s);
   gather_rows(D->swr, S1, D->vrows, Tv, S1, B.swr, S1, s);
   // (discrete actions: int32 moved as 4-byte words)
   gather_rows(D->continuous ? D->prev_action_f : reinterpret_cast<const float*>(D->prev_action), A, D->vrows, Tv, A,
@@ -1937,8 +1970,7 @@ int dgrad_post_ln2(const Ctx& c, const float* dY, int ldy, const float* W, const
   g.ln2_g = c.P(V.ln1_w); g.ln2_x = V.s1; g.ln2_stats = V.st1; g.ln2_out = ds_b; g.ln2_part = P;
   g.ln2_part_b = P + d;
   if (int rc = gemm_run(g, 0, 1, EPI_LN_BWD2, c.s)) return rc;
-  hipLaunchKernelGGL(k_colsum_final, dim3(blocks(4 * d, CS_COLS)), dim3(64 * CS_WAVES), 0, c.s, P, nb, 4 * d,
-                     c.G(V.ln1_w));
+  colsum_final(P, nb, 4 * d, c.G(V.ln1_w), c.s);
   XTRL_LAUNCHED("fractal dgrad_post_ln2");
   return XTRL_OK;
 }
@@ -2000,18 +2032,15 @@ int fractal_train_forward(const XtrlTrainDesc* D, const XtrlFractalTrainDesc* F,
   if ((rc = linear_fwd(c, D->swr, S + 1, c.P(D->w_se), c.P(D->b_se), D->ac_in + d, D->in_dim, T, d, S, EPI_NONE)))
     return rc;
   if (D->evolutionary) {
-    hipLaunchKernelGGL(k_latent_embed, dim3(blocks(D->b * d, 256)), dim3(256), 0, s, D->latent, c.P(D->w_lat),
-                       c.P(D->b_lat), D->lat_e, D->b, D->G, d);
-    hipLaunchKernelGGL(k_rows_bcast_ep, dim3(blocks((int64_t)T * d, 256)), dim3(256), 0, s, D->lat_e, D->ac_in + 2 * d,
-                       D->in_dim, T, D->n, d);
+    latent_embed(D->latent, c.P(D->w_lat), c.P(D->b_lat), D->lat_e, D->b, D->G, d, s);
+    rows_bcast_ep(D->lat_e, D->ac_in + 2 * d, D->in_dim, T, D->n, d, s);
   }
   if (D->continuous) {
     if ((rc = linear_fwd(c, D->next_action_f, D->A, c.P(D->act_emb), c.P(D->act_emb_b), D->ewa + d, 2 * d, T, d, D->A,
                          EPI_NONE)))
       return rc;
   } else {
-    hipLaunchKernelGGL(k_action_rows, dim3(blocks((int64_t)T * d, 256)), dim3(256), 0, s, D->next_action,
-                       c.P(D->act_emb), D->A, D->ewa + d, 2 * d, T, d);
+    action_rows(D->next_action, c.P(D->act_emb), D->A, D->ewa + d, 2 * d, T, d, s);
   }
   XTRL_LAUNCHED("fractal inputs");
   for (int l = 0; l < Lv; ++l) {
@@ -2086,7 +2115,8 @@ int fractal_train_backward(const XtrlTrainDesc* D, const XtrlFractalTrainDesc* F
     if ((rc = wgrad(cw, D->dewa + d, 2 * d, D->next_action_f, D->A, c.G(D->act_emb), T, d, D->A, c.G(D->act_emb_b))))
       return rc;
   } else {
-    if ((rc = B.embed_grad(nullptr, 0, nullptr, D->dewa + d, 2 * d, D->next_action, c.G(D->act_emb)))) return rc;
+    if ((rc = embed_grad(c, B.what, nullptr, 0, nullptr, D->dewa + d, 2 * d, D->next_action, c.G(D->act_emb))))
+      return rc;
     if ((rc = Fk.fork())) return rc;   // (keeps the event count independent of the action kind)
   }
   // final aggregation: feat = hfa W_fa2^T + b; hfa = ReLU(cat W_fa0^T + b)
@@ -2175,7 +2205,210 @@ int fractal_train_backward(const XtrlTrainDesc* D, const XtrlFractalTrainDesc* F
   return B.finish();   // bucket Lv + 1: embeddings, global state, level embeddings
 }
 
+// ============================================================================================
+// The kernel-level test entry (XtrlRowsDesc, include/xtrl_hip.h): one launch (or launcher call) of the row
+// kernels above through the launchers the learn steps call.  Every argument check returns before a launch.
+namespace {
+template <class T>
+const T* rin(const XtrlRowsDesc* R, int i) { return static_cast<const T*>(R->in[i]); }
+template <class T>
+T* rout(const XtrlRowsDesc* R, int i) { return static_cast<T*>(R->out[i]); }
+
+// the descriptor a Ctx-taking launcher reads: sizes, the norm kind and the partial-sum workspace
+XtrlTrainDesc rows_train_desc(const XtrlRowsDesc* R, int b, int n, int d, int A, int rms) {
+  XtrlTrainDesc D{};
+  D.b = b; D.n = n; D.d = d; D.A = A; D.rms_norm = rms;
+  D.part = R->part; D.part_floats = R->part_floats;
+  return D;
+}
+
+int learn_rows(const XtrlRowsDesc* R, int op, hipStream_t s) {
+  XTRL_REQUIRE(R, "learn_rows: null descriptor");
+  const int32_t* n = R->n;
+  const int32_t* ld = R->ld;
+  constexpr int kMaxD = 64 * kMaxDPerLane, kGridYZ = 65535;
+  switch (op) {
+    case XTRL_ROWS_EMBED: {
+      const int T = n[0], S = n[2], A = n[3], d = n[4], in_dim = n[5], cont = n[6], evo = n[7], ln = n[9];
+      XTRL_REQUIRE(T > 0 && n[1] > 0 && d > 0 && A > 0 && S > 0, "learn_rows embed: bad sizes");
+      XTRL_REQUIRE(d <= kMaxD, "learn_rows embed: d = %d > %d unsupported", d, kMaxD);
+      XTRL_REQUIRE(!ln || d <= 256, "learn_rows embed: embed_ln needs d <= 256 (d = %d)", d);
+      XTRL_REQUIRE(S <= EMB_MAXS, "learn_rows embed: state_dim %d > %d unsupported", S, EMB_MAXS);
+      XTRL_REQUIRE(cont || A <= EMB_MAXA, "learn_rows embed: %d discrete actions > %d unsupported", A, EMB_MAXA);
+      XTRL_REQUIRE(in_dim >= d * (evo ? 3 : 2), "learn_rows embed: in_dim %d too narrow", in_dim);
+      for (int i = 0; i < 7; ++i) XTRL_REQUIRE(i == 3 ? (!cont || R->in[3]) : R->in[i] != nullptr, "learn_rows embed: null parameter %d", i);
+      XTRL_REQUIRE(cont ? (R->in[8] && R->in[9]) : (R->in[10] && R->in[11]), "learn_rows embed: missing action inputs");
+      XTRL_REQUIRE(!evo || R->in[7], "learn_rows embed: evolutionary needs lat_e");
+      XTRL_REQUIRE(R->out[0] && R->out[1] && R->out[2] && (!ln || (R->in[12] && R->out[3] && R->out[4])),
+                   "learn_rows embed: null output");
+      EmbedArgs ea{rin<float>(R, 0), rin<float>(R, 1), rin<float>(R, 2), rin<float>(R, 3), rin<float>(R, 4),
+                   rin<float>(R, 5), rin<float>(R, 6), rin<float>(R, 7), rin<float>(R, 8), rin<float>(R, 9),
+                   rin<int32_t>(R, 10), rin<int32_t>(R, 11), rout<float>(R, 0), rout<float>(R, 1), rout<float>(R, 2),
+                   T, n[1], S, A, d, in_dim, cont, evo, R->f[0], ln ? rin<float>(R, 12) : nullptr,
+                   ln ? rout<float>(R, 3) : nullptr, ln ? rout<float>(R, 4) : nullptr, n[8], rin<int32_t>(R, 13)};
+      embed_rows(ea, ln != 0, s);
+      XTRL_LAUNCHED("learn_rows embed");
+      return XTRL_OK;
+    }
+    case XTRL_ROWS_LATENT_EMBED:
+      XTRL_REQUIRE(n[0] > 0 && n[1] > 0 && n[2] > 0 && R->in[0] && R->in[1] && R->in[2] && R->out[0],
+                   "learn_rows latent_embed: bad arguments");
+      latent_embed(rin<float>(R, 0), rin<float>(R, 1), rin<float>(R, 2), rout<float>(R, 0), n[0], n[1], n[2], s);
+      XTRL_LAUNCHED("learn_rows latent_embed");
+      return XTRL_OK;
+    case XTRL_ROWS_LN_FWD:
+    case XTRL_ROWS_LN_BWD: {
+      const int T = n[0], d = n[1];
+      XTRL_REQUIRE(T > 0 && d > 0, "learn_rows ln: bad sizes");
+      XTRL_REQUIRE(d <= kMaxD, "learn_rows ln: d = %d > %d unsupported", d, kMaxD);
+      const XtrlTrainDesc D = rows_train_desc(R, 1, T, d, 0, n[2]);
+      const Ctx c{&D, s, T};
+      if (op == XTRL_ROWS_LN_FWD) {
+        XTRL_REQUIRE(R->in[0] && R->in[1] && R->out[0] && R->out[2], "learn_rows ln_fwd: null operand");
+        return ln_fwd(c, rin<float>(R, 0), rin<float>(R, 1), rout<float>(R, 0), ld[0], rout<float>(R, 1), ld[1],
+                      rout<float>(R, 2));
+      }
+      XTRL_REQUIRE(R->in[0] && R->in[2] && R->in[3] && R->in[4] && R->out[0] && R->out[1] && R->part,
+                   "learn_rows ln_bwd: null operand");
+      return ln_bwd(c, rin<float>(R, 0), ld[0], R->f[0], rin<float>(R, 1), ld[1], rin<float>(R, 2), rin<float>(R, 3),
+                    rin<float>(R, 4), rin<float>(R, 5), rout<float>(R, 0), rout<float>(R, 1), rout<float>(R, 2));
+    }
+    case XTRL_ROWS_QKV_PREP:
+    case XTRL_ROWS_QKV_PREP_BWD: {
+      const int T = n[0], nn = n[1], b = n[2], H = n[3], Hkv = n[4], dh = n[5], rot = n[6], mix_col = n[7];
+      XTRL_REQUIRE(dh == 16 || dh == 32 || dh == 64, "learn_rows qkv_prep: dh = %d is not 16 / 32 / 64", dh);
+      XTRL_REQUIRE(T > 0 && nn > 0 && b > 0 && H > 0 && Hkv > 0 && Hkv <= H && H % Hkv == 0, "learn_rows qkv_prep: bad sizes");
+      XTRL_REQUIRE(rot > 0 && rot % 2 == 0, "learn_rows qkv_prep: bad rot_dim %d", rot);
+      const int I = H * dh, Ikv = Hkv * dh, nq3 = I + 2 * Ikv;
+      XTRL_REQUIRE(ld[0] >= nq3 && (mix_col < 0 || (mix_col >= nq3 && mix_col + Hkv <= ld[0] && ld[1] >= nq3)),
+                   "learn_rows qkv_prep: n_qkv %d / mix column %d / ld_vfirst %d", ld[0], mix_col, ld[1]);
+      XTRL_REQUIRE(R->in[3] ? T <= kGridYZ : (nn <= kGridYZ && b <= kGridYZ && T == b * nn),
+                   "learn_rows qkv_prep: %d tokens (b %d, n %d) exceed the grid", T, b, nn);
+      XTRL_REQUIRE(R->in[0] && R->in[2] && R->out[0] && (mix_col < 0 || R->in[1]), "learn_rows qkv_prep: null operand");
+      if (op == XTRL_ROWS_QKV_PREP) {
+        PrepArgs pa{rin<float>(R, 0), rin<float>(R, 1), rout<float>(R, 0), rin<float>(R, 2), T, nn, H, dh, I, ld[0],
+                    ld[1], rot, mix_col, n[8], R->f[0], rin<int32_t>(R, 3), Ikv};
+        qkv_prep(pa, b, s);
+        XTRL_LAUNCHED("learn_rows qkv_prep");
+        return XTRL_OK;
+      }
+      XTRL_REQUIRE(R->out[1], "learn_rows qkv_prep_bwd: null dvfirst");
+      PrepBwdArgs pb{rout<float>(R, 0), rin<float>(R, 0), rin<float>(R, 1), rout<float>(R, 1), rin<float>(R, 2), T, nn,
+                     H, dh, I, ld[0], ld[1], rot, mix_col, n[9], n[10], n[8], R->f[0], rin<int32_t>(R, 3), Ikv};
+      qkv_prep_bwd(pb, b, s);
+      XTRL_LAUNCHED("learn_rows qkv_prep_bwd");
+      return XTRL_OK;
+    }
+    case XTRL_ROWS_COLSUM: {
+      XTRL_REQUIRE(n[0] > 0 && n[1] > 0 && R->in[0] && R->out[0] && R->part, "learn_rows colsum: bad arguments");
+      const XtrlTrainDesc D = rows_train_desc(R, 1, n[0], 1, 0, 0);
+      return colsum(Ctx{&D, s, n[0]}, rin<float>(R, 0), ld[0], n[0], n[1], rout<float>(R, 0), rin<float>(R, 1), ld[1],
+                    R->f[0]);
+    }
+    case XTRL_ROWS_COLSUM_FINAL:
+      XTRL_REQUIRE(n[0] > 0 && n[1] > 0 && R->in[0] && R->out[0], "learn_rows colsum_final: bad arguments");
+      colsum_final(rin<float>(R, 0), n[0], n[1], rout<float>(R, 0), s);
+      XTRL_LAUNCHED("learn_rows colsum_final");
+      return XTRL_OK;
+    case XTRL_ROWS_COLSUM_QUEUE: {
+      XTRL_REQUIRE(R->jobs && R->n_jobs > 0 && R->part && R->part_floats > 0, "learn_rows colsum queue: bad arguments");
+      for (int j = 0; j < R->n_jobs; ++j) {
+        const XtrlColsumJob& J = R->jobs[j];
+        XTRL_REQUIRE(J.part && J.dst && J.chunks > 0 && J.cols > 0, "learn_rows colsum queue: bad job %d", j);
+        XTRL_REQUIRE((int64_t)J.chunks * J.cols <= R->part_floats,
+                     "learn_rows colsum queue: job %d (%d x %d) exceeds the workspace of %lld floats", j, J.chunks,
+                     J.cols, (long long)R->part_floats);
+      }
+      ColsumQueue q;
+      q.base = R->part;
+      q.cap = R->part_floats;
+      for (int j = 0; j < R->n_jobs; ++j) {   // the plane the producer (here: a copy of the job's partials) fills
+        const XtrlColsumJob& J = R->jobs[j];
+        int rc;
+        float* P = q.take_or_flush(J.chunks, J.cols, J.dst, s, &rc);
+        if (rc) return rc;
+        XTRL_REQUIRE(P, "learn_rows colsum queue: no plane for job %d", j);
+        if (hipMemcpyAsync(P, J.part, sizeof(float) * (size_t)J.chunks * J.cols, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+          set_error("learn_rows colsum queue: copy of job %d failed", j);
+          return XTRL_E_HIP;
+        }
+      }
+      return q.flush(s);
+    }
+    case XTRL_ROWS_EMBED_GRAD: {
+      const int T = n[0], d = n[1], A = n[2];
+      XTRL_REQUIRE(T > 0 && d > 0 && A > 0 && A <= EMB_MAXA, "learn_rows embed_grad: bad sizes (A = %d)", A);
+      XTRL_REQUIRE(d <= kMaxD, "learn_rows embed_grad: d = %d > %d unsupported", d, kMaxD);
+      XTRL_REQUIRE(R->in[2] && R->in[3] && R->out[0] && R->part && (!R->in[1] || R->in[0]),
+                   "learn_rows embed_grad: null operand");
+      XTRL_REQUIRE((int64_t)A * d <= R->part_floats, "learn_rows embed_grad: partial-sum workspace too small");
+      const XtrlTrainDesc D = rows_train_desc(R, 1, T, d, A, 0);
+      return embed_grad(Ctx{&D, s, T}, "learn_rows", rin<float>(R, 0), ld[0], rin<int32_t>(R, 1), rin<float>(R, 2),
+                        ld[1], rin<int32_t>(R, 3), rout<float>(R, 0));
+    }
+    case XTRL_ROWS_LATENT_GRAD:
+      XTRL_REQUIRE(n[1] > 0 && n[2] > 0 && n[3] > 0 && n[4] > 0 && n[0] >= 0 && ld[0] >= n[0] + n[3],
+                   "learn_rows latent_grad: bad sizes");
+      XTRL_REQUIRE(n[3] <= kMaxD, "learn_rows latent_grad: d = %d > %d unsupported", n[3], kMaxD);
+      XTRL_REQUIRE(R->in[0] && R->in[2] && R->out[0] && R->out[1] && R->part, "learn_rows latent_grad: null operand");
+      return latent_grads(rin<float>(R, 0), ld[0], n[0], n[1], n[2], n[3], n[4], rin<int32_t>(R, 1), rin<float>(R, 2),
+                          R->part, R->part_floats, rout<float>(R, 0), rout<float>(R, 1), s);
+    case XTRL_ROWS_VALID_ROWS:
+      XTRL_REQUIRE(n[0] > 0 && n[0] <= VR_MAXB && n[1] > 0 && n[2] >= 0 && n[2] <= n[0] * n[1],
+                   "learn_rows valid_rows: b = %d (<= %d), n = %d, Tv = %d", n[0], VR_MAXB, n[1], n[2]);
+      XTRL_REQUIRE(R->in[0] && R->out[0] && R->out[1], "learn_rows valid_rows: null operand");
+      valid_rows(rin<int32_t>(R, 0), n[0], n[1], n[2], rout<int32_t>(R, 0), rout<int32_t>(R, 1), rout<int32_t>(R, 2), s);
+      XTRL_LAUNCHED("learn_rows valid_rows");
+      return XTRL_OK;
+    case XTRL_ROWS_GATHER:
+    case XTRL_ROWS_SCATTER:
+      XTRL_REQUIRE(n[0] > 0 && n[1] > 0 && ld[0] >= n[1] && ld[1] >= n[1] && R->in[0] && R->in[1] && R->out[0],
+                   "learn_rows gather / scatter: bad arguments");
+      if (op == XTRL_ROWS_GATHER) gather_rows(rin<float>(R, 0), ld[0], rin<int32_t>(R, 1), n[0], n[1], rout<float>(R, 0), ld[1], s);
+      else scatter_rows(rin<float>(R, 0), ld[0], rin<int32_t>(R, 1), n[0], n[1], rout<float>(R, 0), ld[1], s);
+      XTRL_LAUNCHED("learn_rows gather / scatter");
+      return XTRL_OK;
+    case XTRL_ROWS_CAUSAL_MEAN: {
+      XTRL_REQUIRE(n[0] > 0 && n[1] > 0 && n[2] > 0 && ld[0] >= n[2] && ld[2] >= n[2] && R->in[0] && R->out[0] &&
+                       (!R->in[1] || ld[1] >= n[2]),
+                   "learn_rows causal_mean: bad arguments");
+      XTRL_REQUIRE(n[2] <= kMaxD, "learn_rows causal_mean: d = %d > %d unsupported", n[2], kMaxD);
+      const XtrlTrainDesc D = rows_train_desc(R, n[0], n[1], n[2], 0, 0);
+      return causal_mean(Ctx{&D, s, n[0] * n[1]}, rin<float>(R, 0), ld[0], rin<float>(R, 1), ld[1], rout<float>(R, 0),
+                         ld[2], n[3] != 0);
+    }
+    case XTRL_ROWS_AXPB: {
+      XTRL_REQUIRE(n[0] > 0 && n[1] > 0 && (ld[0] == 0 || ld[0] >= n[1]) && ld[2] >= n[1] && R->in[0] && R->out[0] &&
+                       (!R->in[1] || ld[1] >= n[1]),
+                   "learn_rows rows_axpb: bad arguments");
+      const XtrlTrainDesc D = rows_train_desc(R, 1, n[0], 1, 0, 0);
+      return rows_axpb(Ctx{&D, s, n[0]}, rin<float>(R, 0), ld[0], R->f[0], rin<float>(R, 1), ld[1], rout<float>(R, 0),
+                       ld[2], n[0], n[1]);
+    }
+    case XTRL_ROWS_ACTION_ROWS:
+      XTRL_REQUIRE(n[0] > 0 && n[1] > 0 && n[2] > 0 && ld[0] >= n[1] && R->in[0] && R->in[1] && R->out[0],
+                   "learn_rows action_rows: bad arguments");
+      action_rows(rin<int32_t>(R, 0), rin<float>(R, 1), n[2], rout<float>(R, 0), ld[0], n[0], n[1], s);
+      XTRL_LAUNCHED("learn_rows action_rows");
+      return XTRL_OK;
+    case XTRL_ROWS_BCAST_EP:
+      XTRL_REQUIRE(n[0] > 0 && n[1] > 0 && n[2] > 0 && ld[0] >= n[2] && R->in[0] && R->out[0],
+                   "learn_rows rows_bcast_ep: bad arguments");
+      rows_bcast_ep(rin<float>(R, 0), rout<float>(R, 0), ld[0], n[0], n[1], n[2], s);
+      XTRL_LAUNCHED("learn_rows rows_bcast_ep");
+      return XTRL_OK;
+    default:
+      XTRL_REQUIRE(false, "learn_rows: unknown op %d", op);
+  }
+  return XTRL_OK;
+}
+}  // namespace
+
 }  // namespace xtrl
+
+extern "C" int xtrl_learn_rows(const XtrlRowsDesc* desc, int op, void* stream) {
+  return xtrl::learn_rows(desc, op, xtrl::as_stream(stream));
+}
 
 extern "C" int xtrl_train_forward(const XtrlTrainDesc* desc, void* stream) {
   return xtrl::train_forward(desc, xtrl::as_stream(stream));

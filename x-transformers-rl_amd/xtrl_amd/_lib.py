@@ -13,7 +13,7 @@ from pathlib import Path
 import torch   # noqa: F401  (load torch's HIP runtime first so the library binds to the same one)
 
 LIB_PATH = Path(os.environ.get('XTRL_LIB', Path(__file__).resolve().parent / 'libxtrl_hip.so'))   # override: A/B experiments
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 P = C.c_void_p
 I32, I64, U32, U64, F32 = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
@@ -174,6 +174,23 @@ class GemmDesc(C.Structure):
                                     'ln2_part_b')])
 
 
+# ops of xtrl_learn_rows (XTRL_ROWS_*)
+ROWS_OPS = ('EMBED', 'LATENT_EMBED', 'LN_FWD', 'LN_BWD', 'QKV_PREP', 'QKV_PREP_BWD', 'COLSUM', 'COLSUM_FINAL',
+            'COLSUM_QUEUE', 'EMBED_GRAD', 'LATENT_GRAD', 'VALID_ROWS', 'GATHER', 'SCATTER', 'CAUSAL_MEAN', 'AXPB',
+            'ACTION_ROWS', 'BCAST_EP')
+ROWS = {name: i for i, name in enumerate(ROWS_OPS)}
+
+
+class ColsumJob(C.Structure):
+    _fields_ = [('part', P), ('dst', P), ('chunks', I32), ('cols', I32)]
+
+
+class RowsDesc(C.Structure):
+    """One launch of a learn-step row kernel (XtrlRowsDesc, xtrl_learn_rows): the kernel-level tests' entry."""
+    _fields_ = [('in_', P * 16), ('out', P * 6), ('ld', I32 * 4), ('n', I32 * 12), ('f', F32 * 2), ('part', P),
+                ('part_floats', I64), ('jobs', C.POINTER(ColsumJob)), ('n_jobs', I32)]
+
+
 class BatchDesc(C.Structure):
     _fields_ = ([(n, I32) for n in ('N', 'Tmax', 'n', 'b', 'S', 'A', 'B', 'continuous')]
                 + [(n, P) for n in ('states', 'actions', 'actions_f', 'rewards', 'logp', 'bounds', 'values', 'returns',
@@ -189,6 +206,7 @@ SIGNATURES = {
     'xtrl_gemm_f32': (I32, [P, I32, P, I32, P, P, P, I32, P, I32, P, I64, I32, I32, I32, I32, P]),
     'xtrl_gemm_ex': (I32, [I32, I32, P, I32, P, I32, P, P, I32, I32, I32, I32, F32, P]),
     'xtrl_gemm_epi': (I32, [C.POINTER(GemmDesc), I32, I32, I32, P]),
+    'xtrl_learn_rows': (I32, [C.POINTER(RowsDesc), I32, P]),
     'xtrl_gemm_wgrad': (I32, [P, I32, P, I32, P, I32, I32, I32, I32, F32, P, I64, P]),
     'xtrl_gemm_wgrad_db': (I32, [P, I32, P, I32, P, I32, I32, I32, I32, F32, P, I64, P, I32, P]),
     'xtrl_linear_gelu_drop': (I32, [P, I32, P, P, P, I32, P, I32, I32, I32, I32, F32, U64, U32, U32, P]),
@@ -284,7 +302,7 @@ STRUCTS = {'XtrlDecodeLayer': DecodeLayer, 'XtrlRngState': RngState, 'XtrlDecode
            'XtrlLossDesc': LossDesc, 'XtrlFractalLevel': FractalLevel, 'XtrlFractalDesc': FractalDesc,
            'XtrlFractalTrainLevel': FractalTrainLevel, 'XtrlFractalTrainDesc': FractalTrainDesc,
            'XtrlWimgEntry': WimgEntry, 'XtrlWfragEntry': WfragEntry,
-           'XtrlGemmDesc': GemmDesc}
+           'XtrlGemmDesc': GemmDesc, 'XtrlRowsDesc': RowsDesc, 'XtrlColsumJob': ColsumJob}
 
 _lib = None
 
