@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 31
+#define XTRL_ABI_VERSION 32
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -480,6 +480,49 @@ typedef struct XtrlFractalDesc {
 /* one timestep of the fractal policy for the live rows of `desc` (xtrl_rollout_begin first; the
  * level sums are zeroed by the caller at the start of an episode batch) */
 int xtrl_fractal_decode_step(const XtrlDecodeDesc* desc, const XtrlFractalDesc* fd, int t, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Kernel-level test entry of the decode step (ABI 32; no reference counterpart): ONE call of a launcher of
+ * csrc/decode.hip — the function xtrl_decode_step / xtrl_fractal_decode_step themselves call, not a copy — at
+ * step t, after the steps' own descriptor checks (with `fd`: the fractal step's).  The caller owns every buffer
+ * of the descriptor the launcher touches and the state it expects (live_rows / live_count of parity t & 1 for
+ * every op but EMBED, the caches' rows < t, ...).  Argument errors (NULL descriptor, t or layer out of range,
+ * unknown op, a form the descriptor does not select, a bad projection shape) return XTRL_E_ARG and launch
+ * nothing.  xtrl_decode_step_rows, xtrl_rollout_begin, xtrl_rollout_env_feedback and xtrl_sim_reset are entries
+ * of one launch each already.
+ *   EMBED         launch_embed: compaction (E > 8192: its own launch first) + embeddings of step t; args n[0] != 0:
+ *                 the embedding also writes xn = norm(x) layers[0].ln_attn
+ *   ATTN          launch_attn_decode of `layer`; fd non-NULL and the fused form: the fractal post-norm tail (FrPost)
+ *                 exactly as the fractal step builds it for level `layer`
+ *   MLP           launch_mlp of `layer` (the layer must select the one-launch feed-forward); fd non-NULL: the
+ *                 fractal level's call with its LayerNorm-3 / running-mean tail
+ *   HEADS         decode_heads; args n[0]: final_norm (the one-launch heads need 0)
+ *   PROJ          one decode projection over the live rows: in: A, W (fragment-packed), bias, gamma, R, row_map i32,
+ *                 row_map2 i32 (any but A, W may be NULL); out: C, C2; ld: lda, ldr, ldc, ldc2; n: K, ln_k, N,
+ *                 epi (XTRL_EPI_NONE / GELU / SILU / RELU), n_split (>= N: no split; else columns >= n_split go to
+ *                 C2 [row_map2[m]][n - n_split]); the norm kind is the descriptor's rms_norm
+ *   GLU           hglu = value * gelu(gate) of hff (ff_glu)
+ *   FR_LN12       fractal level `layer`: x2 = LN2(LN1(x + tmp) + c)       (needs fd)
+ *   FR_LN3_TAIL   fractal level `layer`: x3 = LN3(tmp), sums, mean, the next level's input (needs fd)
+ *   COPY_ROWS     the fractal step's copy of g into allf's last column block (needs fd) */
+#define XTRL_DECODE_EMBED 0
+#define XTRL_DECODE_ATTN 1
+#define XTRL_DECODE_MLP 2
+#define XTRL_DECODE_HEADS 3
+#define XTRL_DECODE_PROJ 4
+#define XTRL_DECODE_GLU 5
+#define XTRL_DECODE_FR_LN12 6
+#define XTRL_DECODE_FR_LN3_TAIL 7
+#define XTRL_DECODE_COPY_ROWS 8
+
+typedef struct XtrlDecodeOpArgs {
+  const void* in[8];
+  void* out[2];
+  int32_t ld[4];
+  int32_t n[6];
+} XtrlDecodeOpArgs;
+int xtrl_decode_op(const XtrlDecodeDesc* desc, const XtrlFractalDesc* fd, const XtrlDecodeOpArgs* args, int op,
+                   int layer, int t, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * HL-Gauss value decode + GAE   (xtrl.py:843-852 -> calc_gae :616-640, HLGaussLoss value)

@@ -24,7 +24,8 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert set(_lib.SIGNATURES) <= declared | {'xtrl_last_error'}
-    assert lib.xtrl_abi_version() == _lib.ABI_VERSION
+    assert {'xtrl_gemm_epi', 'xtrl_learn_rows', 'xtrl_decode_op'} <= declared & set(_lib.SIGNATURES)   # the test entries
+    assert lib.xtrl_abi_version() == _lib.ABI_VERSION >= 32
 
 
 def test_env_switches_are_documented():

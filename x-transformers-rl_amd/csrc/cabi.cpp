@@ -49,7 +49,8 @@ extern "C" int64_t xtrl_struct_size(const char* name) {
                {"XtrlFractalDesc", sizeof(XtrlFractalDesc)},     {"XtrlFractalTrainLevel", sizeof(XtrlFractalTrainLevel)},
                {"XtrlFractalTrainDesc", sizeof(XtrlFractalTrainDesc)}, {"XtrlWimgEntry", sizeof(XtrlWimgEntry)},
                {"XtrlWfragEntry", sizeof(XtrlWfragEntry)},           {"XtrlGemmDesc", sizeof(XtrlGemmDesc)},
-               {"XtrlRowsDesc", sizeof(XtrlRowsDesc)},               {"XtrlColsumJob", sizeof(XtrlColsumJob)}};
+               {"XtrlRowsDesc", sizeof(XtrlRowsDesc)},               {"XtrlColsumJob", sizeof(XtrlColsumJob)},
+               {"XtrlDecodeOpArgs", sizeof(XtrlDecodeOpArgs)}};
   for (const auto& s : sizes)
     if (name && strcmp(name, s.name) == 0) return s.size;
   return -1;

@@ -1494,6 +1494,12 @@ __global__ void k_glu_rows(const XtrlDecodeDesc D, int t) {
   D.hglu[(int64_t)r * ff + j] = u[j] * geluf_(u[ff + j]);
 }
 
+int glu_rows(const XtrlDecodeDesc* D, int t, hipStream_t s) {
+  hipLaunchKernelGGL(k_glu_rows, dim3((unsigned)(((int64_t)D->E * D->ff + 255) / 256)), dim3(256), 0, s, *D, t);
+  XTRL_LAUNCHED("glu_rows");
+  return XTRL_OK;
+}
+
 int dproj(const XtrlDecodeDesc* D, int t, const float* A, int lda, const float* W, int K, const float* bias,
           const float* gamma, int ln_k, const float* R, int ldr, float* C, int ldc, int N, int epi, hipStream_t s,
           const int32_t* row_map = nullptr, int n_split = 1 << 30, float* C2 = nullptr, int ldc2 = 0,
@@ -2354,8 +2360,7 @@ int decode_step(const XtrlDecodeDesc* D, int t, hipStream_t s) {
       if ((rc = dproj(D, t, xn_ff ? D->xn : D->x, d, Ly.w_ff1, d, Ly.b_ff1, xn_ff ? nullptr : Ly.ln_ff,
                       xn_ff ? 0 : d, nullptr, 0, D->hff, 2 * ff, 2 * ff, EPI_NONE, s)))
         return rc;
-      hipLaunchKernelGGL(k_glu_rows, dim3((unsigned)(((int64_t)D->E * ff + 255) / 256)), dim3(256), 0, s, *D, t);
-      XTRL_LAUNCHED("glu_rows");
+      if ((rc = glu_rows(D, t, s))) return rc;
     } else if ((rc = dproj(D, t, xn_ff ? D->xn : D->x, d, Ly.w_ff1, d, Ly.b_ff1, xn_ff ? nullptr : Ly.ln_ff,
                            xn_ff ? 0 : d, nullptr, 0, D->hff, ff, ff, EPI_GELU, s))) {
       return rc;
@@ -2404,7 +2409,9 @@ int decode_step_rows(const XtrlDecodeDesc* D, int t, int max_rows, hipStream_t s
   return XTRL_OK;
 }
 
-int fractal_decode_step(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int t, hipStream_t s) {
+namespace {
+
+int check_fractal(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int t) {
   if (int rc = check_desc(D)) return rc;
   XTRL_REQUIRE(F && F->level && F->levels == D->L && F->levels > 0, "fractal_decode: levels mismatch");
   XTRL_REQUIRE(t >= 0 && t < D->Tmax, "fractal_decode: t=%d outside [0, %d)", t, D->Tmax);
@@ -2413,8 +2420,67 @@ int fractal_decode_step(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int t
                "fractal_decode: the descriptor must describe plain attention (n_qkv = 3 I) with state_only = 1");
   XTRL_REQUIRE(F->g_init && F->c0 && F->g && F->c2 && F->tmp && F->x2 && F->mean && F->allf && F->hagg,
                "fractal_decode: missing buffers");
-  const int E = D->E, d = D->d, I = D->H * D->dh, ff = D->ff, Lv = F->levels;
-  const dim3 rows_grid((E + 3) / 4), rows_blk(256);
+  return XTRL_OK;
+}
+
+// level l's post-norm tail of the attention launch: x2 = LN2(LN1(x + attn W_out^T) + c)
+FrPost fr_post(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int l) {
+  const XtrlFractalLevel& Q = F->level[l];
+  FrPost fp;
+  fp.g1 = Q.ln1_w; fp.b1 = Q.ln1_b; fp.g2 = Q.ln2_w; fp.b2 = Q.ln2_b;
+  fp.c = l > 0 ? F->c2 : F->c0; fp.ldc = l > 0 ? D->d : 0; fp.out = F->x2; fp.eps = F->ln_eps;
+  return fp;
+}
+
+// whether level l's feed-forward runs as one launch (k_mlp, FrMlp tail)
+bool fr_mlp_fused(const XtrlDecodeDesc* D, int l) {
+  return D->mlp_part && D->mlp_cnt && mlp_weights(D->layers[l]) && D->d % 64 == 0 && D->d <= 256 &&
+         D->ff % MLP_HW == 0;
+}
+
+const float* fr_le_next(const XtrlFractalDesc* F, int l) {
+  return l + 1 < F->levels ? F->level[l + 1].level_emb : nullptr;
+}
+
+FrMlp fr_mlp(const XtrlFractalDesc* F, int l) {
+  const XtrlFractalLevel& Q = F->level[l];
+  FrMlp fm;
+  fm.g3 = Q.ln3_w; fm.b3 = Q.ln3_b; fm.sums = Q.sums; fm.mean = F->mean; fm.le_next = fr_le_next(F, l); fm.eps = F->ln_eps;
+  return fm;
+}
+
+// the row-kernel forms of level l's tails (not fused): x2 from the out-projection in F->tmp ...
+int fr_ln12(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int l, int t, hipStream_t s) {
+  const XtrlFractalLevel& Q = F->level[l];
+  hipLaunchKernelGGL(k_fr_ln12, dim3((D->E + 3) / 4), dim3(256), 0, s, *D, t, F->tmp, l > 0 ? F->c2 : F->c0,
+                     l > 0 ? D->d : 0, Q.ln1_w, Q.ln1_b, Q.ln2_w, Q.ln2_b, F->x2, F->ln_eps);
+  XTRL_LAUNCHED("fractal ln12");
+  return XTRL_OK;
+}
+
+// ... and x3, the running sums / mean and the next level's input from s3 in F->tmp
+int fr_ln3_tail(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int l, int t, hipStream_t s) {
+  const XtrlFractalLevel& Q = F->level[l];
+  hipLaunchKernelGGL(k_fr_ln3_tail, dim3((D->E + 3) / 4), dim3(256), 0, s, *D, t, F->tmp, Q.ln3_w, Q.ln3_b, Q.sums,
+                     F->mean, fr_le_next(F, l), F->ln_eps);
+  XTRL_LAUNCHED("fractal ln3 tail");
+  return XTRL_OK;
+}
+
+// the global state g into the last column block of allf
+int fr_copy_g(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, hipStream_t s) {
+  const int E = D->E, d = D->d, Lv = F->levels;
+  hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)(((int64_t)E * d + 255) / 256)), dim3(256), 0, s, F->g, 2 * d,
+                     F->allf + (int64_t)Lv * d, (Lv + 1) * d, E, d);
+  XTRL_LAUNCHED("copy_rows");
+  return XTRL_OK;
+}
+
+}  // namespace
+
+int fractal_decode_step(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int t, hipStream_t s) {
+  if (int rc = check_fractal(D, F, t)) return rc;
+  const int d = D->d, I = D->H * D->dh, ff = D->ff, Lv = F->levels;
   if (int rc = launch_embed(D, t, nullptr, s)) return rc;   // x = W_in s + b_in + le_0
   int rc;
   for (int l = 0; l < Lv; ++l) {
@@ -2427,9 +2493,7 @@ int fractal_decode_step(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int t
       return rc;
     // x2 = LN2(LN1(x + attn W_out^T) + c): inside the attention launch (one workgroup per live row,
     // the head partials of the out-projection meeting in LDS) or as projection + row kernel
-    FrPost fp;
-    fp.g1 = Q.ln1_w; fp.b1 = Q.ln1_b; fp.g2 = Q.ln2_w; fp.b2 = Q.ln2_b;
-    fp.c = l > 0 ? F->c2 : F->c0; fp.ldc = l > 0 ? d : 0; fp.out = F->x2; fp.eps = F->ln_eps;
+    const FrPost fp = fr_post(D, F, l);
     const bool fused = attn_fused(D, l);
     if (D->prof_events) (void)hipEventRecord((hipEvent_t)D->prof_events[2 * (t * D->L + l)], s);
     if ((rc = launch_attn_decode(D, l, t, s, fused ? fp : FrPost{}))) return rc;
@@ -2437,28 +2501,18 @@ int fractal_decode_step(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int t
     if (!fused) {
       if ((rc = dproj(D, t, D->att, I, Q.w_out, I, nullptr, nullptr, 0, nullptr, 0, F->tmp, d, d, EPI_NONE, s)))
         return rc;
-      hipLaunchKernelGGL(k_fr_ln12, rows_grid, rows_blk, 0, s, *D, t, F->tmp, l > 0 ? F->c2 : F->c0, l > 0 ? d : 0,
-                         Q.ln1_w, Q.ln1_b, Q.ln2_w, Q.ln2_b, F->x2, F->ln_eps);
-      XTRL_LAUNCHED("fractal ln12");
+      if ((rc = fr_ln12(D, F, l, t, s))) return rc;
     }
     // s3 = x2 + FF(x2): one launch (k_mlp, split-bf16 weight images) or the two projections
-    const XtrlDecodeLayer& Ly = D->layers[l];
-    const bool mlp = D->mlp_part && D->mlp_cnt && mlp_weights(Ly) && d % 64 == 0 && d <= 256 &&
-                     ff % MLP_HW == 0;
     // x3 = LN3(s3), its running mean, the next level's input: in the k_mlp tail, or a row kernel
-    const float* le_next = l + 1 < Lv ? F->level[l + 1].level_emb : nullptr;
-    if (mlp) {
-      FrMlp fm;
-      fm.g3 = Q.ln3_w; fm.b3 = Q.ln3_b; fm.sums = Q.sums; fm.mean = F->mean; fm.le_next = le_next; fm.eps = F->ln_eps;
-      if ((rc = launch_mlp_rows(D, l, t, F->x2, F->x2, nullptr, d, nullptr, nullptr, 0, s, fm))) return rc;
+    if (fr_mlp_fused(D, l)) {
+      if ((rc = launch_mlp_rows(D, l, t, F->x2, F->x2, nullptr, d, nullptr, nullptr, 0, s, fr_mlp(F, l)))) return rc;
     } else {
       if ((rc = dproj(D, t, F->x2, d, Q.w_ff1, d, Q.b_ff1, nullptr, 0, nullptr, 0, D->hff, ff, ff, EPI_GELU, s)))
         return rc;
       if ((rc = dproj(D, t, D->hff, ff, Q.w_ff2, ff, Q.b_ff2, nullptr, 0, F->x2, d, F->tmp, d, d, EPI_NONE, s)))
         return rc;
-      hipLaunchKernelGGL(k_fr_ln3_tail, rows_grid, rows_blk, 0, s, *D, t, F->tmp, Q.ln3_w, Q.ln3_b, Q.sums, F->mean,
-                         le_next, F->ln_eps);
-      XTRL_LAUNCHED("fractal ln3 tail");
+      if ((rc = fr_ln3_tail(D, F, l, t, s))) return rc;
     }
     // [g | p_l] = [g | 0] + mean [W_gu; W_p,l]^T + [b_gu; b_p,l]: g in place (level 0 from g_init),
     // the level projection into allf
@@ -2466,9 +2520,7 @@ int fractal_decode_step(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int t
                     2 * d, 2 * d, EPI_NONE, s, nullptr, d, F->allf + (int64_t)l * d, (Lv + 1) * d)))
       return rc;
   }
-  hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)(((int64_t)E * d + 255) / 256)), dim3(256), 0, s, F->g, 2 * d,
-                     F->allf + (int64_t)Lv * d, (Lv + 1) * d, E, d);
-  XTRL_LAUNCHED("copy_rows");
+  if ((rc = fr_copy_g(D, F, s))) return rc;
   // final aggregation -> the heads' input row (no final norm: the encoder has none)
   if ((rc = dproj(D, t, F->allf, (Lv + 1) * d, F->w_fa0, (Lv + 1) * d, F->b_fa0, nullptr, 0, nullptr, 0, F->hagg,
                   2 * d, 2 * d, EPI_RELU, s)))
@@ -2557,7 +2609,74 @@ int sim_reset(float* state, int E, int S, uint64_t seed, uint32_t update, const 
   return XTRL_OK;
 }
 
+// ============================================================================================
+// The kernel-level test entry (XtrlDecodeOpArgs, include/xtrl_hip.h): ONE call of a launcher the steps
+// above call — the function itself, not a copy — after their descriptor checks.  Every argument check
+// returns before a launch.
+int decode_op(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, const XtrlDecodeOpArgs* a, int op, int l, int t,
+              hipStream_t s) {
+  if (int rc = F ? check_fractal(D, F, t) : check_desc(D)) return rc;
+  XTRL_REQUIRE(t >= 0 && t < D->Tmax, "decode_op: t=%d outside [0, %d)", t, D->Tmax);
+  XTRL_REQUIRE(l >= 0 && l < D->L, "decode_op: layer %d outside [0, %d)", l, D->L);
+  const int32_t zero[6] = {0, 0, 0, 0, 0, 0};
+  const int32_t* n = a ? a->n : zero;
+  switch (op) {
+    case XTRL_DECODE_EMBED:
+      XTRL_REQUIRE(!n[0] || (D->xn && D->layers[0].ln_attn), "decode_op embed: the pre-norm needs xn and layer 0's gain");
+      return launch_embed(D, t, n[0] ? D->layers[0].ln_attn : nullptr, s);
+    case XTRL_DECODE_ATTN: {
+      const bool fused = attn_fused(D, l);
+      XTRL_REQUIRE(D->qkv && D->layers[l].k_cache && D->layers[l].v_cache &&
+                       (fused ? (D->x && (F || D->layers[l].ln_ff)) : D->att != nullptr),
+                   "decode_op attn: missing q|k|v, cache, output or residual buffers");
+      return launch_attn_decode(D, l, t, s, (F && fused) ? fr_post(D, F, l) : FrPost{});
+    }
+    case XTRL_DECODE_MLP:
+      if (F) {
+        XTRL_REQUIRE(fr_mlp_fused(D, l), "decode_op mlp: level %d has no one-launch feed-forward", l);
+        return launch_mlp_rows(D, l, t, F->x2, F->x2, nullptr, D->d, nullptr, nullptr, 0, s, fr_mlp(F, l));
+      }
+      XTRL_REQUIRE(mlp_fused(D, l), "decode_op mlp: layer %d has no one-launch feed-forward", l);
+      return launch_mlp(D, l, t, s);
+    case XTRL_DECODE_HEADS:
+      return decode_heads(D, t, n[0] != 0, s);
+    case XTRL_DECODE_PROJ: {
+      XTRL_REQUIRE(a, "decode_op proj: null arguments");
+      const int32_t* ld = a->ld;
+      const bool split = n[4] < n[2];
+      return dproj(D, t, static_cast<const float*>(a->in[0]), ld[0], static_cast<const float*>(a->in[1]), n[0],
+                   static_cast<const float*>(a->in[2]), static_cast<const float*>(a->in[3]), n[1],
+                   static_cast<const float*>(a->in[4]), ld[1], static_cast<float*>(a->out[0]), ld[2], n[2], n[3], s,
+                   static_cast<const int32_t*>(a->in[5]), split ? n[4] : 1 << 30,
+                   split ? static_cast<float*>(a->out[1]) : nullptr, split ? ld[3] : 0,
+                   split ? static_cast<const int32_t*>(a->in[6]) : nullptr);
+    }
+    case XTRL_DECODE_GLU:
+      XTRL_REQUIRE(D->ff_glu && D->ff > 0, "decode_op glu: the descriptor has no ff_glu");
+      return glu_rows(D, t, s);
+    case XTRL_DECODE_FR_LN12:
+      XTRL_REQUIRE(F && D->x && F->level[l].ln1_w && F->level[l].ln1_b && F->level[l].ln2_w && F->level[l].ln2_b,
+                   "decode_op fr_ln12: needs the fractal descriptor with the level's norm1 / norm2");
+      return fr_ln12(D, F, l, t, s);
+    case XTRL_DECODE_FR_LN3_TAIL:
+      XTRL_REQUIRE(F && F->level[l].sums && F->level[l].ln3_w && F->level[l].ln3_b && (l + 1 == F->levels || D->x),
+                   "decode_op fr_ln3_tail: needs the fractal descriptor");
+      return fr_ln3_tail(D, F, l, t, s);
+    case XTRL_DECODE_COPY_ROWS:
+      XTRL_REQUIRE(F, "decode_op copy_rows: needs the fractal descriptor");
+      return fr_copy_g(D, F, s);
+    default:
+      XTRL_REQUIRE(false, "decode_op: unknown op %d", op);
+  }
+  return XTRL_OK;
+}
+
 }  // namespace xtrl
+
+extern "C" int xtrl_decode_op(const XtrlDecodeDesc* desc, const XtrlFractalDesc* fd, const XtrlDecodeOpArgs* args,
+                              int op, int layer, int t, void* stream) {
+  return xtrl::decode_op(desc, fd, args, op, layer, t, xtrl::as_stream(stream));
+}
 
 extern "C" int xtrl_decode_step_rows(const XtrlDecodeDesc* desc, int t, int max_rows, void* stream) {
   return xtrl::decode_step_rows(desc, t, max_rows, xtrl::as_stream(stream));

@@ -13,7 +13,7 @@ from pathlib import Path
 import torch   # noqa: F401  (load torch's HIP runtime first so the library binds to the same one)
 
 LIB_PATH = Path(os.environ.get('XTRL_LIB', Path(__file__).resolve().parent / 'libxtrl_hip.so'))   # override: A/B experiments
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 P = C.c_void_p
 I32, I64, U32, U64, F32 = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
@@ -191,6 +191,16 @@ class RowsDesc(C.Structure):
                 ('part_floats', I64), ('jobs', C.POINTER(ColsumJob)), ('n_jobs', I32)]
 
 
+# ops of xtrl_decode_op (XTRL_DECODE_*)
+DECODE_OPS = ('EMBED', 'ATTN', 'MLP', 'HEADS', 'PROJ', 'GLU', 'FR_LN12', 'FR_LN3_TAIL', 'COPY_ROWS')
+DECODE_OP = {name: i for i, name in enumerate(DECODE_OPS)}
+
+
+class DecodeOpArgs(C.Structure):
+    """Operands of one launcher call of the decode step (XtrlDecodeOpArgs, xtrl_decode_op): the kernel-level tests' entry."""
+    _fields_ = [('in_', P * 8), ('out', P * 2), ('ld', I32 * 4), ('n', I32 * 6)]
+
+
 class BatchDesc(C.Structure):
     _fields_ = ([(n, I32) for n in ('N', 'Tmax', 'n', 'b', 'S', 'A', 'B', 'continuous')]
                 + [(n, P) for n in ('states', 'actions', 'actions_f', 'rewards', 'logp', 'bounds', 'values', 'returns',
@@ -207,6 +217,7 @@ SIGNATURES = {
     'xtrl_gemm_ex': (I32, [I32, I32, P, I32, P, I32, P, P, I32, I32, I32, I32, F32, P]),
     'xtrl_gemm_epi': (I32, [C.POINTER(GemmDesc), I32, I32, I32, P]),
     'xtrl_learn_rows': (I32, [C.POINTER(RowsDesc), I32, P]),
+    'xtrl_decode_op': (I32, [C.POINTER(DecodeDesc), C.POINTER(FractalDesc), C.POINTER(DecodeOpArgs), I32, I32, I32, P]),
     'xtrl_gemm_wgrad': (I32, [P, I32, P, I32, P, I32, I32, I32, I32, F32, P, I64, P]),
     'xtrl_gemm_wgrad_db': (I32, [P, I32, P, I32, P, I32, I32, I32, I32, F32, P, I64, P, I32, P]),
     'xtrl_linear_gelu_drop': (I32, [P, I32, P, P, P, I32, P, I32, I32, I32, I32, F32, U64, U32, U32, P]),
@@ -302,7 +313,8 @@ STRUCTS = {'XtrlDecodeLayer': DecodeLayer, 'XtrlRngState': RngState, 'XtrlDecode
            'XtrlLossDesc': LossDesc, 'XtrlFractalLevel': FractalLevel, 'XtrlFractalDesc': FractalDesc,
            'XtrlFractalTrainLevel': FractalTrainLevel, 'XtrlFractalTrainDesc': FractalTrainDesc,
            'XtrlWimgEntry': WimgEntry, 'XtrlWfragEntry': WfragEntry,
-           'XtrlGemmDesc': GemmDesc, 'XtrlRowsDesc': RowsDesc, 'XtrlColsumJob': ColsumJob}
+           'XtrlGemmDesc': GemmDesc, 'XtrlRowsDesc': RowsDesc, 'XtrlColsumJob': ColsumJob,
+           'XtrlDecodeOpArgs': DecodeOpArgs}
 
 _lib = None
 
