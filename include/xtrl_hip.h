@@ -27,7 +27,7 @@ extern "C" {
 #define XTRL_E_ARG 1    /* invalid argument / unsupported shape */
 #define XTRL_E_HIP 2    /* HIP launch or runtime error */
 
-#define XTRL_ABI_VERSION 32
+#define XTRL_ABI_VERSION 33
 
 int xtrl_abi_version(void);
 /* sizeof(struct) of a descriptor type named by its C name (-1: unknown); host-only */
@@ -143,6 +143,23 @@ int xtrl_gemm_wgrad_db(const float* dY, int ldy, const float* X, int ldx, float*
 /* Y[m, :] = layer_norm(X[m, :]) * gamma  (x-transformers LayerNorm, final norm of the Decoder) */
 int xtrl_layernorm_f32(const float* X, int ldx, const float* gamma, float* Y, int ldy, int M, int D, void* stream);
 
+/* Per-head output gates (x-transformers Attention gate_value_heads): the learn step's two row passes, exported
+ * for the kernel-level tests (tests/test_attn_head_gate_gpu.py); the learn step runs these same launchers.
+ * T tokens, H query heads of dh in {16, 32, 64} channels, I = H dh; with s[t, h] = sigmoid(proj[t, hg_col + h]):
+ *   fwd   og[t, h dh + c] = src[t, h dh + c] s[t, h]                                   (src == og: in place)
+ *   bwd   on entry dog holds C, the out-projection's input gradient (already times the element gate's sigmoid
+ *         where there is one);  dproj[t, hg_col + h] = (sum_c C[t, h, c] o[t, h, c]) s (1 - s);
+ *         dog[t, h, c] = C s in place;  gate_col >= 0: dproj[t, gate_col + h dh + c] *= s (the element gate's
+ *         logit gradients, written without the head gate by the DGATE epilogue);  gate_col = -1: none
+ * src / og / dog / o: 16-byte aligned, leading dimensions >= I and multiples of 4.  proj / dproj: any leading
+ * dimension >= the columns named (the gate columns are read and written as scalars unless the launch finds
+ * them 16-byte aligned).  No other column of dproj is touched.  T H must fit an int.  Every check runs before
+ * the launch; T = 0 launches nothing. */
+int xtrl_head_gate_fwd(const float* src, int ld_src, const float* proj, int ld_proj, float* og, int ld_og, int T, int H,
+                       int dh, int hg_col, void* stream);
+int xtrl_head_gate_bwd(float* dog, int ld_dog, const float* o, int ld_o, const float* proj, int ld_proj, float* dproj,
+                       int ld_dproj, int T, int H, int dh, int hg_col, int gate_col, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Rollout: one timestep of the vectorised policy for E concurrent episodes.
  * Replaces the per-step body of Learner.forward (xtrl.py:1250-1341): RSNorm eval (:1254-1259),
@@ -153,7 +170,7 @@ typedef struct XtrlDecodeLayer {
   const float* ln_attn;  /* [d]  pre-attention LayerNorm gamma */
   /* decode GEMM weights (w_qkv, w_out, w_ff1, w_ff2, w_h1, w_h2) are fragment-packed (xtrl_dgemm_pack)
    * images of the nn.Linear weights described */
-  const float* w_qkv;    /* [n_qkv][d]  rows: to_q [I] | to_k [Ikv] | to_v [Ikv] | to_v_gate [I] (opt) | value-residual mix [Hkv] (opt);
+  const float* w_qkv;    /* [n_qkv][d]  rows: to_q [I] | to_k [Ikv] | to_v [Ikv] | to_v_gate [I] (opt) | value-residual mix [Hkv] (opt) | to_v_head_gate [H] (opt, head_gate);
                             I = H dh, Ikv = Hkv dh */
   const float* b_qkv;    /* [n_qkv]     zeros for q/k/v */
   const float* w_out;    /* [d][I]      to_out */
@@ -330,6 +347,12 @@ typedef struct XtrlDecodeDesc {
    * 0 stays 0.  On top of the rotary, the window, the sinks, ALiBi and qk-norm (the score's scale is
    * attn_scale then).  No parameter.  0: off */
   float attn_softclamp;
+  /* per-head output gates (ABI 33): world_model['attn_gate_value_heads'] (x-transformers Attention
+   * to_v_head_gate, arXiv 2306.12929).  The projection row carries H more columns, the head-gate logits, as its
+   * last: n_qkv = I + 2 Ikv (+ I gate) (+ Hkv mix) + H, and the finished attention row of query head h is
+   * multiplied by sigmoid(qkv[n_qkv - H + h]) — after the softmax . V with the sinks, on top of the
+   * element-wise gate_values gate where both are on.  One gate per query head whatever Hkv is.  0: off */
+  int head_gate;
   /* attention sinks (ABI 25): world_model['attn_num_mem_kv'] learned memory key / value rows per kv head
    * (XtrlDecodeLayer.mem_k / mem_v; no rotary) and world_model['attn_add_zero_kv'], one all-zero key /
    * value ("+ 1" in the softmax denominator).  The step-t query attends its cached keys (the window's)
@@ -708,7 +731,7 @@ int xtrl_attn_bwd_part_softclamp(const float* q, const float* k, const float* v,
  * ------------------------------------------------------------------------------------------- */
 typedef struct XtrlTrainLayer {
   int64_t ln_attn, w_proj, b_proj, w_out, ln_ff, w_ff1, b_ff1, w_ff2, b_ff2;
-  int n_qkv;            /* I + 2 Ikv (+ I value gates) (+ Hkv value-residual mix, layers >= 2); Ikv = Hkv dh (XtrlTrainDesc.Hkv) */
+  int n_qkv;            /* I + 2 Ikv (+ I value gates) (+ Hkv value-residual mix, layers >= 2) (+ H head gates); Ikv = Hkv dh (XtrlTrainDesc.Hkv) */
   int mix;              /* learned value-residual mix in this layer */
   float* x_attn;        /* [T][d] residual stream entering the attention block */
   float* x_ff;          /* [T][d] entering the feed-forward block */
@@ -716,7 +739,7 @@ typedef struct XtrlTrainLayer {
   float* xn_ff;
   float* st_attn;       /* [T][2] LayerNorm (mean, rstd) */
   float* st_ff;
-  float* proj;          /* [T][n_qkv] q | k | v | gate | mix pre-activations */
+  float* proj;          /* [T][n_qkv] q | k | v | gate | mix | head gate pre-activations */
   float* qkv;           /* [T][I + 2 Ikv] rotary q, k and (mixed) v */
   float* o;             /* [T][I] attention output */
   float* og;            /* [T][I] gated output (== o when there are no value gates) */
@@ -902,6 +925,12 @@ typedef struct XtrlTrainDesc {
    * columns' scores to c tanh(score / c) in every layer; the attention runs as xtrl_attn_fwd_softclamp /
    * xtrl_attn_bwd_part_softclamp on the token rows.  No scratch, no parameter.  0: off */
   float attn_softclamp;
+  /* per-head output gates (ABI 33), as XtrlDecodeDesc.head_gate: every layer's projection row ends with H
+   * head-gate logit columns (XtrlTrainLayer.n_qkv counts them, w_proj / b_proj hold to_v_head_gate's rows and
+   * bias after the mix's).  Forward: one row pass after the attention (xtrl_head_gate_fwd) into og, which must
+   * then be a buffer of its own, as with gate_values.  Backward: one row pass after the out-projection's input
+   * gradient (xtrl_head_gate_bwd).  0: off */
+  int head_gate;
   /* attention sinks (ABI 25), as XtrlDecodeDesc: num_mem_kv memory key / value rows per kv head at
    * XtrlTrainLayer.mem_k / mem_v (their gradients land at the same offsets of grad, inside the layer's
    * bucket) and add_zero_kv; the attention runs as xtrl_attn_fwd_sink / xtrl_attn_bwd_part_sink on the

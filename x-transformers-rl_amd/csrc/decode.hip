@@ -596,6 +596,21 @@ __global__ __launch_bounds__(FJ > 0 ? 512 : 256) void k_attn_decode(const XtrlDe
     if constexpr (FUSE) *reinterpret_cast<float4*>(qs + 4 * cq) = make_float4(o4[0], o4[1], o4[2], o4[3]);
     else *reinterpret_cast<float4*>(D.att + (int64_t)r * I + h * DH + 4 * cq) = make_float4(o4[0], o4[1], o4[2], o4[3]);
   }
+  // Per-head output gate (D.head_gate, wave-uniform): the lane scales the quad it has just stored by
+  // sigmoid(the row's logit n_qkv - H + h).  A pass of its own behind a compiler memory barrier, not a factor
+  // on o4: the code above then compiles to the arithmetic it had before the option existed — a factor on o4
+  // changed how the vectoriser packed the P.V accumulation (which products are fused into the sums), and with
+  // it the last bits of a rollout that does not use the option.  r and h are the wave's: the logit's address
+  // is formed on the scalar unit
+  if (D.head_gate && kk == 0) {
+    asm volatile("" ::: "memory");
+    float4* po = FUSE ? reinterpret_cast<float4*>(qs + 4 * cq)
+                      : reinterpret_cast<float4*>(D.att + (int64_t)r * I + h * DH + 4 * cq);
+    const int rs = __builtin_amdgcn_readfirstlane(r), hs = __builtin_amdgcn_readfirstlane(h);
+    const float hg = sigmoidf_(D.qkv[(int64_t)rs * D.n_qkv + (D.n_qkv - H + hs)]);
+    const float4 o = *po;
+    *po = make_float4(o.x * hg, o.y * hg, o.z * hg, o.w * hg);
+  }
   if constexpr (FUSE) {
     wave_sync();
     float* part = smem + nw * (D.Tmax + 3 * DH);   // [H][d] partial output rows
@@ -1035,8 +1050,9 @@ int check_desc(const XtrlDecodeDesc* D) {
   XTRL_REQUIRE(D->Hkv >= 0 && D->Hkv <= D->H && D->H % (D->Hkv > 0 ? D->Hkv : D->H) == 0,
                "decode: Hkv %d must divide H %d (0 = H)", D->Hkv, D->H);
   const int Hkv = D->Hkv > 0 ? D->Hkv : D->H;
-  XTRL_REQUIRE(D->n_qkv == I + 2 * Hkv * D->dh + (D->gate_values ? I : 0) + ((D->value_residual && D->learned_mix) ? Hkv : 0),
-               "decode: n_qkv mismatch (I + 2 Ikv (+ I gate) (+ Hkv mix))");
+  XTRL_REQUIRE(D->n_qkv == I + 2 * Hkv * D->dh + (D->gate_values ? I : 0) + ((D->value_residual && D->learned_mix) ? Hkv : 0) +
+                                (D->head_gate ? D->H : 0),
+               "decode: n_qkv mismatch (I + 2 Ikv (+ I gate) (+ Hkv mix) (+ H head gate))");
   XTRL_REQUIRE(!D->ff_glu || (D->hglu && D->hff), "decode: ff_glu needs hglu");
   XTRL_REQUIRE(D->attn_window >= 0, "decode: attn_window %d < 0 (0 = no window)", D->attn_window);
   XTRL_REQUIRE(D->num_mem_kv >= 0 && D->num_mem_kv <= kMaxMemKV, "decode: num_mem_kv %d outside [0, %d]", D->num_mem_kv,
@@ -2245,6 +2261,15 @@ __global__ __launch_bounds__(ROW_T) void k_decode_row(const XtrlDecodeDesc D, in
           }
           *reinterpret_cast<float4*>(att + h * DH + 4 * cq) = make_float4(o4[0], o4[1], o4[2], o4[3]);
         }
+        // per-head output gate, as in k_attn_decode: the lane rescales the quad it has just stored, in a pass
+        // of its own behind a compiler memory barrier, so the code above keeps the arithmetic it had
+        if (D.head_gate && kk == 0) {
+          asm volatile("" ::: "memory");
+          float4* po = reinterpret_cast<float4*>(att + h * DH + 4 * cq);
+          const float hg = sigmoidf_(qkv[D.n_qkv - H + h]);
+          const float4 o = *po;
+          *po = make_float4(o.x * hg, o.y * hg, o.z * hg, o.w * hg);
+        }
       }
       __syncthreads();
       mark();
@@ -2415,7 +2440,7 @@ int check_fractal(const XtrlDecodeDesc* D, const XtrlFractalDesc* F, int t) {
   if (int rc = check_desc(D)) return rc;
   XTRL_REQUIRE(F && F->level && F->levels == D->L && F->levels > 0, "fractal_decode: levels mismatch");
   XTRL_REQUIRE(t >= 0 && t < D->Tmax, "fractal_decode: t=%d outside [0, %d)", t, D->Tmax);
-  XTRL_REQUIRE(D->state_only && !D->gate_values && !D->value_residual && !D->rotary_abs && !D->qk_norm &&
+  XTRL_REQUIRE(D->state_only && !D->gate_values && !D->head_gate && !D->value_residual && !D->rotary_abs && !D->qk_norm &&
                    D->n_qkv == 3 * D->H * D->dh && D->d <= 64 * FR_MAXF,
                "fractal_decode: the descriptor must describe plain attention (n_qkv = 3 I) with state_only = 1");
   XTRL_REQUIRE(F->g_init && F->c0 && F->g && F->c2 && F->tmp && F->x2 && F->mean && F->allf && F->hagg,

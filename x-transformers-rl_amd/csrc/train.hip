@@ -535,6 +535,72 @@ __global__ __launch_bounds__(PREP_T) void k_qkv_prep_bwd(const PrepBwdArgs a) {
   }
 }
 
+// ---- per-head output gates (x-transformers Attention gate_value_heads) -----------------
+// s[t, h] = sigmoid(proj[t, hg_col + h]) scales head h's attention output of token t.  DH / 4 consecutive
+// lanes own one (token, head): a float4 of the head's channels each (the [T][I] operands have leading
+// dimensions that are multiples of 4 and 16-byte aligned bases: checked by the launchers).  The grid is
+// flat over the T H groups, HG_T / (DH / 4) of them per block, with a tail guard.  The gate columns of proj
+// / dproj have any leading dimension (n_qkv % 4 may be 1, 2, 3): scalar accesses, except the element gate's
+// columns where the launcher found them 16-byte aligned (vec).
+struct HeadGateArgs {
+  const float* src;     // fwd: [T][ld_a] attention output (o, or og as the attention kernel gated it)
+  float* og;            // fwd: [T][ld_b] gated output (may be src)
+  float* dog;           // bwd: [T][ld_a] C on entry, C s on exit
+  const float* o;       // bwd: [T][ld_b] attention output (ungated)
+  const float* proj;    // [T][ld_proj]
+  float* dproj;         // bwd: [T][ld_dproj]
+  int ld_a, ld_b, ld_proj, ld_dproj, T, H, hg_col, gate_col, vec;   // gate_col < 0: no element gate
+};
+constexpr int HG_T = 256;
+
+template <int DH>
+__global__ __launch_bounds__(HG_T) void k_head_gate_fwd(const HeadGateArgs a) {
+  constexpr int G = DH / 4;
+  const int grp = blockIdx.x * (HG_T / G) + threadIdx.x / G, j = threadIdx.x % G;
+  if (grp >= a.T * a.H) return;
+  const int t = grp / a.H, h = grp - t * a.H, col = h * DH + 4 * j;
+  const float s = sigmoidf_(a.proj[(int64_t)t * a.ld_proj + a.hg_col + h]);
+  float4 v = *reinterpret_cast<const float4*>(a.src + (int64_t)t * a.ld_a + col);
+  v = make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
+  *reinterpret_cast<float4*>(a.og + (int64_t)t * a.ld_b + col) = v;
+}
+
+template <int DH>
+__global__ __launch_bounds__(HG_T) void k_head_gate_bwd(const HeadGateArgs a) {
+  constexpr int G = DH / 4;
+  const int grp0 = blockIdx.x * (HG_T / G) + threadIdx.x / G, j = threadIdx.x % G;
+  const bool valid = grp0 < a.T * a.H;   // (every lane takes part in the shuffles: G aligned lanes a group)
+  const int grp = valid ? grp0 : 0;
+  const int t = grp / a.H, h = grp - t * a.H, col = h * DH + 4 * j;
+  float* gp = a.dog + (int64_t)t * a.ld_a + col;
+  float4 c4 = make_float4(0.f, 0.f, 0.f, 0.f), o4 = c4;
+  float x = 0.f;
+  if (valid) {
+    c4 = *reinterpret_cast<const float4*>(gp);
+    o4 = *reinterpret_cast<const float4*>(a.o + (int64_t)t * a.ld_b + col);
+    x = a.proj[(int64_t)t * a.ld_proj + a.hg_col + h];
+  }
+  const float s = sigmoidf_(x);
+  float dot = (c4.x * o4.x + c4.y * o4.y) + (c4.z * o4.z + c4.w * o4.w);
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) dot += __shfl_xor(dot, off, 64);
+  if (!valid) return;
+  *reinterpret_cast<float4*>(gp) = make_float4(c4.x * s, c4.y * s, c4.z * s, c4.w * s);
+  float* dp = a.dproj + (int64_t)t * a.ld_dproj;
+  // s (1 - s) as sigmoid(x) sigmoid(-x): 1 - s cancels for a gate that is nearly open (relative error 2^-24 / (1 - s))
+  if (j == 0) dp[a.hg_col + h] = dot * s * sigmoidf_(-x);
+  if (a.gate_col >= 0) {   // the element gate's logit gradients (wave-uniform branches)
+    float* ge = dp + a.gate_col + col;
+    if (a.vec) {
+      float4 g4 = *reinterpret_cast<const float4*>(ge);
+      *reinterpret_cast<float4*>(ge) = make_float4(g4.x * s, g4.y * s, g4.z * s, g4.w * s);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ge[i] *= s;
+    }
+  }
+}
+
 // ---- deterministic column sums: part[chunk][c] = sum over the chunk's rows of w_r * src[r][c] --
 __global__ __launch_bounds__(256) void k_colsum_part(const float* src, int ld, int rows, int cols, int chunk_rows,
                                                      const float* rw, int ld_rw, float rw_scale, float* part) {
@@ -924,6 +990,54 @@ void qkv_prep(const PrepArgs& a, int b, hipStream_t s) {
 void qkv_prep_bwd(const PrepBwdArgs& a, int b, hipStream_t s) {
   const unsigned pb = blocks((a.I + 2 * a.Ikv) / 2, PREP_T);
   hipLaunchKernelGGL(k_qkv_prep_bwd, a.rows ? dim3(pb, a.T) : dim3(pb, a.n, b), dim3(PREP_T), 0, s, a);
+}
+// per-head output gates: the forward and backward row passes (xtrl_head_gate_fwd / _bwd are these launchers).
+// Every check comes before the launch
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int head_gate_check(const char* what, const void* a, int ld_a, const void* b, int ld_b, const void* proj, int ld_proj,
+                    int T, int H, int dh, int hg_col) {
+  XTRL_REQUIRE(dh == 16 || dh == 32 || dh == 64, "%s: dim_head %d unsupported (16 / 32 / 64)", what, dh);
+  XTRL_REQUIRE(T >= 0 && H > 0 && H <= 4096 / dh, "%s: bad sizes (T %d, H %d)", what, T, H);
+  XTRL_REQUIRE((int64_t)T * H <= INT32_MAX, "%s: T H = %lld groups are beyond the grid", what, (long long)T * H);
+  XTRL_REQUIRE(a && b && proj, "%s: null operand", what);
+  XTRL_REQUIRE(ld_a >= H * dh && ld_b >= H * dh && ld_a % 4 == 0 && ld_b % 4 == 0 && aligned16(a) && aligned16(b),
+               "%s: the [T][I] operands need leading dimensions >= I = %d, multiples of 4, and 16-byte aligned bases", what,
+               H * dh);
+  XTRL_REQUIRE(hg_col >= 0 && ld_proj >= hg_col + H, "%s: head-gate columns %d .. %d outside the row of %d", what, hg_col,
+               hg_col + H, ld_proj);
+  return XTRL_OK;
+}
+int head_gate_fwd(const float* src, int ld_src, const float* proj, int ld_proj, float* og, int ld_og, int T, int H, int dh,
+                  int hg_col, hipStream_t s) {
+  if (int rc = head_gate_check("head_gate_fwd", src, ld_src, og, ld_og, proj, ld_proj, T, H, dh, hg_col)) return rc;
+  if (T == 0) return XTRL_OK;
+  HeadGateArgs a{src, og, nullptr, nullptr, proj, nullptr, ld_src, ld_og, ld_proj, 0, T, H, hg_col, -1, 0};
+  const dim3 grid(blocks((int64_t)T * H, HG_T / (dh / 4)));
+  if (dh == 16) hipLaunchKernelGGL(k_head_gate_fwd<16>, grid, dim3(HG_T), 0, s, a);
+  else if (dh == 32) hipLaunchKernelGGL(k_head_gate_fwd<32>, grid, dim3(HG_T), 0, s, a);
+  else hipLaunchKernelGGL(k_head_gate_fwd<64>, grid, dim3(HG_T), 0, s, a);
+  XTRL_LAUNCHED("head_gate_fwd");
+  return XTRL_OK;
+}
+int head_gate_bwd(float* dog, int ld_dog, const float* o, int ld_o, const float* proj, int ld_proj, float* dproj,
+                  int ld_dproj, int T, int H, int dh, int hg_col, int gate_col, hipStream_t s) {
+  if (int rc = head_gate_check("head_gate_bwd", dog, ld_dog, o, ld_o, proj, ld_proj, T, H, dh, hg_col)) return rc;
+  const int I = H * dh;
+  XTRL_REQUIRE(dproj && ld_dproj >= hg_col + H, "head_gate_bwd: dproj missing or its row of %d without columns %d .. %d",
+               ld_dproj, hg_col, hg_col + H);
+  XTRL_REQUIRE(gate_col == -1 || (gate_col >= 0 && gate_col + I <= ld_dproj &&
+                                  (gate_col + I <= hg_col || gate_col >= hg_col + H)),
+               "head_gate_bwd: element-gate columns %d .. %d outside the row of %d or over the head-gate columns", gate_col,
+               gate_col + I, ld_dproj);
+  if (T == 0) return XTRL_OK;
+  const int vec = gate_col >= 0 && gate_col % 4 == 0 && ld_dproj % 4 == 0 && aligned16(dproj);
+  HeadGateArgs a{nullptr, nullptr, dog, o, proj, dproj, ld_dog, ld_o, ld_proj, ld_dproj, T, H, hg_col, gate_col, vec};
+  const dim3 grid(blocks((int64_t)T * H, HG_T / (dh / 4)));
+  if (dh == 16) hipLaunchKernelGGL(k_head_gate_bwd<16>, grid, dim3(HG_T), 0, s, a);
+  else if (dh == 32) hipLaunchKernelGGL(k_head_gate_bwd<32>, grid, dim3(HG_T), 0, s, a);
+  else hipLaunchKernelGGL(k_head_gate_bwd<64>, grid, dim3(HG_T), 0, s, a);
+  XTRL_LAUNCHED("head_gate_bwd");
+  return XTRL_OK;
 }
 // the gene conditioning's gradients from dac[:, off : off + d]: the per-episode sums into part [b][d], then
 // dw [d][G] and db [d] accumulated
@@ -1331,8 +1445,12 @@ int validate(const XtrlTrainDesc* D) {
                  "train: layer %d num_mem_kv %d without mem_k / mem_v offsets or the sink workspace", li, D->num_mem_kv);
   for (int li = 0; li < D->L; ++li)
     XTRL_REQUIRE(D->layers[li].n_qkv == D->H * D->dh + 2 * kv_inner(D) + (D->gate_values ? D->H * D->dh : 0) +
-                                            (D->layers[li].mix ? kv_heads(D) : 0),
-                 "train: layer %d n_qkv %d is not I + 2 Ikv (+ I gate) (+ Hkv mix)", li, D->layers[li].n_qkv);
+                                            (D->layers[li].mix ? kv_heads(D) : 0) + (D->head_gate ? D->H : 0),
+                 "train: layer %d n_qkv %d is not I + 2 Ikv (+ I gate) (+ Hkv mix) (+ H head gate)", li,
+                 D->layers[li].n_qkv);
+  for (int li = 0; li < D->L && D->head_gate; ++li)
+    XTRL_REQUIRE(D->layers[li].og && D->layers[li].og != D->layers[li].o, "train: layer %d head_gate needs og apart from o",
+                 li);
   XTRL_REQUIRE(D->in_dim == D->d * (D->evolutionary ? 3 : 2), "train: in_dim mismatch");
   XTRL_REQUIRE(D->ld_ff == 0 || (D->ld_ff >= D->ff && D->ld_ff % 4 == 0), "train: ld_ff %d (ff %d)", D->ld_ff, D->ff);
   XTRL_REQUIRE(!D->ff_glu || (D->ld_u2 >= 2 * D->ff && D->ld_u2 % 4 == 0 && D->glu_dh),
@@ -1549,6 +1667,7 @@ int train_forward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
   const int32_t* rows = D->packed ? D->vrows : nullptr;
   const int T = c.T, d = D->d, I = D->H * D->dh, ff = D->ff, lf = ld_ff(D);
   const int Ikv = kv_inner(D), nq3 = I + 2 * Ikv;   // the k / v segment width; q | k | v columns of a projection row
+  const bool gated = D->gate_values || D->head_gate;   // the out-projection reads og (either gate), else o
   int rc;
   // the pre-split weight images, from the parameters this step is about to read: first on the stream,
   // reused by this step's backward (XTRL_WIMG=0: none; the lookups then find nothing either)
@@ -1591,12 +1710,17 @@ int train_forward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     if ((rc = attn_fwd_ex(ap, Ly.qkv, Ly.qkv + I, Ly.qkv + I + Ikv, Ly.o, Ly.lse,
                           D->gate_values ? Ly.proj + nq3 : nullptr, D->gate_values ? Ly.og : nullptr, s)))
       return rc;
+    // per-head output gates: og = (og as the attention kernel gated it, else o) * sigmoid(the row's last H logits)
+    if (D->head_gate &&
+        (rc = head_gate_fwd(D->gate_values ? Ly.og : Ly.o, I, Ly.proj, Ly.n_qkv, Ly.og, I, T, D->H, D->dh, Ly.n_qkv - D->H, s)))
+      return rc;
+    const float* attn_out = gated ? Ly.og : Ly.o;   // what the out-projection reads
     if (fuse) {
-      if ((rc = linear_res_ln(c, D->gate_values ? Ly.og : Ly.o, I, c.P(Ly.w_out), nullptr, Ly.x_attn, Ly.x_ff, I,
+      if ((rc = linear_res_ln(c, attn_out, I, c.P(Ly.w_out), nullptr, Ly.x_attn, Ly.x_ff, I,
                               c.P(Ly.ln_ff), Ly.xn_ff, d, nullptr, 0, Ly.st_ff)))
         return rc;
     } else {
-      if ((rc = linear_fwd(c, D->gate_values ? Ly.og : Ly.o, I, c.P(Ly.w_out), nullptr, Ly.x_ff, d, T, d, I, EPI_NONE,
+      if ((rc = linear_fwd(c, attn_out, I, c.P(Ly.w_out), nullptr, Ly.x_ff, d, T, d, I, EPI_NONE,
                            Ly.x_attn)))
         return rc;
       if ((rc = ln_fwd(c, Ly.x_ff, c.P(Ly.ln_ff), Ly.xn_ff, d, nullptr, 0, Ly.st_ff))) return rc;
@@ -1644,6 +1768,7 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
   const int32_t* rows = D->packed ? D->vrows : nullptr;
   const int T = c.T, d = D->d, I = D->H * D->dh, ff = D->ff, lf = ld_ff(D);
   const int Ikv = kv_inner(D), nq3 = I + 2 * Ikv;   // the k / v segment width; q | k | v columns of a projection row
+  const bool gated = D->gate_values || D->head_gate;   // the out-projection reads og (either gate), else o
   int rc;
   // The two modes of this backward.  Fused (ln_fusable): every LayerNorm backward runs in a GEMM
   // epilogue, and every buffer a side-stream weight gradient reads is a per-layer plane written once
@@ -1742,7 +1867,7 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     }
     // attention out-projection (+ residual) and the value gate
     if ((rc = F.fork())) return rc;
-    if ((rc = wgrad(cw, xg, d, D->gate_values ? Ly.og : Ly.o, I, c.G(Ly.w_out), T, d, I))) return rc;
+    if ((rc = wgrad(cw, xg, d, gated ? Ly.og : Ly.o, I, c.G(Ly.w_out), T, d, I))) return rc;
     hipEvent_t e_out = F.mark();
     if (!fuse && (rc = F.wait(e_proj))) return rc;   // the deeper block's projection weight gradient read dproj
     if (D->gate_values) {
@@ -1752,6 +1877,11 @@ int train_backward_rows(const XtrlTrainDesc* D, int Trows, hipStream_t s) {
     } else {
       if ((rc = linear_dgrad(c, xg, d, c.P(Ly.w_out), D->dog, I, T, d, I, EPI_NONE))) return rc;
     }
+    // per-head output gates: the head-gate logit gradients, dog and the element gate's gradients times sigmoid
+    if (D->head_gate &&
+        (rc = head_gate_bwd(D->dog, I, Ly.o, I, Ly.proj, Ly.n_qkv, dproj, Ly.n_qkv, T, D->H, D->dh, Ly.n_qkv - D->H,
+                            D->gate_values ? nq3 : -1, s)))
+      return rc;
     const AttnProblem ap = attn_problem(c, Ly, li);
     if ((rc = attn_bwd_ex(ap, Ly.qkv, Ly.qkv + I, Ly.qkv + I + Ikv, Ly.o, Ly.lse, D->dog, dproj, dproj + I,
                           dproj + I + Ikv, D->delta, s)))
@@ -2523,6 +2653,17 @@ extern "C" int xtrl_linear_gelu_drop(const float* X, int ldx, const float* W, co
   g.drop_thresh8 = xtrl::dropout_thresh8(p);
   g.inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
   return xtrl::gemm_run(g, 0, 0, xtrl::EPI_GELU_DROP, xtrl::as_stream(stream));
+}
+
+extern "C" int xtrl_head_gate_fwd(const float* src, int ld_src, const float* proj, int ld_proj, float* og, int ld_og, int T,
+                                  int H, int dh, int hg_col, void* stream) {
+  return xtrl::head_gate_fwd(src, ld_src, proj, ld_proj, og, ld_og, T, H, dh, hg_col, xtrl::as_stream(stream));
+}
+
+extern "C" int xtrl_head_gate_bwd(float* dog, int ld_dog, const float* o, int ld_o, const float* proj, int ld_proj,
+                                  float* dproj, int ld_dproj, int T, int H, int dh, int hg_col, int gate_col, void* stream) {
+  return xtrl::head_gate_bwd(dog, ld_dog, o, ld_o, proj, ld_proj, dproj, ld_dproj, T, H, dh, hg_col, gate_col,
+                             xtrl::as_stream(stream));
 }
 
 extern "C" int xtrl_glu_drop_fwd(const float* u, int ldu, float* h, int ldh, int M, int ff, float p, uint64_t seed,

@@ -13,7 +13,7 @@ from pathlib import Path
 import torch   # noqa: F401  (load torch's HIP runtime first so the library binds to the same one)
 
 LIB_PATH = Path(os.environ.get('XTRL_LIB', Path(__file__).resolve().parent / 'libxtrl_hip.so'))   # override: A/B experiments
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 P = C.c_void_p
 I32, I64, U32, U64, F32 = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
@@ -56,7 +56,8 @@ class DecodeDesc(C.Structure):
                 + [(n, P) for n in ('w_h1x', 'heads_part', 'heads_cnt', 'row_part', 'row_cnt')]
                 + [('ff_glu', I32), ('hglu', P), ('qk_norm', I32), ('attn_scale', F32), ('xpos_base', F32),
                    ('rms_norm', I32), ('act_host', P), ('attn_window', I32), ('Hkv', I32),
-                   ('alibi_slopes', P), ('attn_softclamp', F32), ('num_mem_kv', I32), ('add_zero_kv', I32)])
+                   ('alibi_slopes', P), ('attn_softclamp', F32), ('head_gate', I32), ('num_mem_kv', I32),
+                   ('add_zero_kv', I32)])
 
 
 class FractalLevel(C.Structure):
@@ -135,7 +136,7 @@ class TrainDesc(C.Structure):
                    ('Hkv', I32), ('wimg', P), ('wimg_bytes', I64), ('wimg_tab', P),
                    ('wimg_tab_host', C.POINTER(WimgEntry)), ('wimg_n', I32), ('alibi_slopes', P),
                    ('wfrag', P), ('wfrag_bytes', I64), ('wfrag_tab', P), ('wfrag_tab_host', C.POINTER(WfragEntry)),
-                   ('wfrag_n', I32), ('attn_softclamp', F32),
+                   ('wfrag_n', I32), ('attn_softclamp', F32), ('head_gate', I32),
                    ('num_mem_kv', I32), ('add_zero_kv', I32), ('sink_ws', P), ('sink_ws_floats', I64)])
 
 
@@ -222,6 +223,8 @@ SIGNATURES = {
     'xtrl_gemm_wgrad_db': (I32, [P, I32, P, I32, P, I32, I32, I32, I32, F32, P, I64, P, I32, P]),
     'xtrl_linear_gelu_drop': (I32, [P, I32, P, P, P, I32, P, I32, I32, I32, I32, F32, U64, U32, U32, P]),
     'xtrl_layernorm_f32': (I32, [P, I32, P, P, I32, I32, I32, P]),
+    'xtrl_head_gate_fwd': (I32, [P, I32, P, I32, P, I32, I32, I32, I32, I32, P]),
+    'xtrl_head_gate_bwd': (I32, [P, I32, P, I32, P, I32, P, I32, I32, I32, I32, I32, I32, P]),
     'xtrl_rollout_begin': (I32, [C.POINTER(DecodeDesc), P]),
     'xtrl_decode_step': (I32, [C.POINTER(DecodeDesc), I32, P]),
     'xtrl_decode_step_rows': (I32, [C.POINTER(DecodeDesc), I32, I32, P]),

@@ -131,7 +131,8 @@ class Agent(nn.Module):
                  'learned_value_residual_mix', 'ff_mult', 'ff_no_bias', 'ff_glu', 'attn_qk_norm',
                  'attn_qk_norm_scale', 'rotary_xpos', 'rotary_xpos_scale_base', 'use_rmsnorm',
                  'attn_max_attend_past', 'attn_one_kv_head', 'attn_num_mem_kv', 'attn_add_zero_kv',
-                 'alibi_pos_bias', 'alibi_num_heads', 'attn_softclamp_logits', 'attn_logit_softclamp_value'}
+                 'alibi_pos_bias', 'alibi_num_heads', 'attn_softclamp_logits', 'attn_logit_softclamp_value',
+                 'attn_gate_value_heads'}
         if 'alibi_learned' in wm:   # (not at its default: those were dropped above)
             raise NotImplementedError('alibi_learned is not supported by the MI355X decoder: the ALiBi slopes are the '
                                       'fixed geometric sequence (alibi_pos_bias), without parameters')
@@ -205,6 +206,11 @@ class Agent(nn.Module):
             if not softclamp_on:
                 raise ValueError(f'attn_logit_softclamp_value={softclamp!r} needs attn_softclamp_logits=True')
         softclamp = float(softclamp) if softclamp_on else 0.
+        # per-head output gates (x-transformers Attention gate_value_heads, arXiv 2306.12929): each query head's
+        # attention output times sigmoid(to_v_head_gate(x)[h]), on top of attn_gate_values where both are on
+        gate_value_heads = wm.get('attn_gate_value_heads', False)
+        if not isinstance(gate_value_heads, (bool, np.bool_)):
+            raise ValueError(f'attn_gate_value_heads must be a bool, not {gate_value_heads!r}')
         self.seed = int(seed)
         self.evolutionary = evolutionary
         self.evolve_every, self.evolve_after_step = evolve_every, evolve_after_step
@@ -224,7 +230,7 @@ class Agent(nn.Module):
                         xpos_scale_base=float(wm.get('rotary_xpos_scale_base', 512.)),
                         rotary_abs_rollout=rotary_abs_rollout, attn_window=int(window or 0), kv_heads=kv_heads,
                         num_mem_kv=int(num_mem_kv), add_zero_kv=bool(add_zero_kv), alibi_heads=alibi_heads,
-                        softclamp=softclamp,
+                        softclamp=softclamp, gate_value_heads=bool(gate_value_heads),
                         hl_reduction_mean=hl_reduction_mean, hl_sigma_ratio=hl_sigma_ratio)
         self.cfg = c
         # the learn step without the minibatch's padding (XtrlTrainDesc.packed): exact only with the
@@ -250,6 +256,9 @@ class Agent(nn.Module):
             if c.softclamp:
                 raise NotImplementedError('the fractal policy body has no logit soft-clamp: leave attn_softclamp_logits '
                                           'at False')
+            if c.gate_value_heads:
+                raise NotImplementedError('the fractal policy body has no per-head output gates: leave '
+                                          'attn_gate_value_heads at False')
             if c.gate_values or c.value_residual or c.ff_no_bias or c.ff_glu or c.qk_norm or c.rotary_xpos or c.rms_norm:
                 raise NotImplementedError('the fractal policy body has no gated values / value residual / bias-free or '
                                           'GLU feed-forward / qk norm / xPos rotary / RMSNorm: set attn_gate_values / '

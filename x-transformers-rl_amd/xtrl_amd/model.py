@@ -58,6 +58,7 @@ class ModelConfig:
     add_zero_kv: bool = False            # x-transformers attn_add_zero_kv: one all-zero key / value ("+ 1" softmax)
     alibi_heads: int = 0                 # x-transformers alibi_pos_bias: heads with an ALiBi slope (alibi_num_heads); 0: off
     softclamp: float = 0.                # x-transformers attn_softclamp_logits: attn_logit_softclamp_value; 0: off
+    gate_value_heads: bool = False       # x-transformers attn_gate_value_heads: one sigmoid output gate per query head
     rotary_abs_rollout: bool = False     # decision log: reference semantics = rotary position 0 in rollout
     hl_reduction_mean: bool = True       # decision log: hl-gauss-pytorch default reduction
     hl_sigma_ratio: float = 2.0
@@ -126,6 +127,13 @@ class XAttention(nn.Module):
             self.to_value_residual_mix = nn.Sequential(nn.Linear(d, c.n_kv_heads))   # one mix per kv head
             nn.init.zeros_(self.to_value_residual_mix[0].weight)
             nn.init.zeros_(self.to_value_residual_mix[0].bias)
+        # per-head output gates (x-transformers Attention gate_value_heads): one logit per query head, whatever
+        # kv_heads is; initialised open (weight 0, bias 10), as x-transformers does
+        self.to_v_head_gate = None
+        if c.gate_value_heads:
+            self.to_v_head_gate = nn.Linear(d, c.heads)
+            nn.init.constant_(self.to_v_head_gate.weight, 0.)
+            nn.init.constant_(self.to_v_head_gate.bias, 10.)
         # attention sinks (x-transformers Attention num_mem_kv): memory keys / values every query sees, one
         # set per kv head; no rotary, no value-residual mix (state-dict names mem_k / mem_v beside to_q)
         if c.num_mem_kv > 0:
@@ -260,7 +268,7 @@ class WorldModelActorCritic(nn.Module):
         """Parameter groups of the flat buffer, bucketed in the order the fused backward completes
         them (train.hip records an event per bucket, include/xtrl_hip.h grad_events): [heads + state /
         gene embeddings + final norm], [decoder block L-1], ..., [block 0], [input embeddings].  A
-        group's names must be adjacent: the q|k|v|gate|mix weights of each attention block, the first
+        group's names must be adjacent: the q|k|v|gate|mix|head-gate weights of each attention block, the first
         actor / critic head layers and to_pred.0 | to_pred_done are one GEMM operand each (views).
         Groups whose size is not a multiple of 4 floats move to the last bucket, so every GEMM weight
         starts 16-byte aligned (float4 operand loads).  -> list of buckets, each a list of groups."""
@@ -284,9 +292,11 @@ class WorldModelActorCritic(nn.Module):
             mix = c.value_residual and c.learned_mix and li > 0
             g = [grp([pre + 'to_q.weight', pre + 'to_k.weight', pre + 'to_v.weight']
                      + ([pre + 'to_v_gate.weight'] if c.gate_values else [])
-                     + ([pre + 'to_value_residual_mix.0.weight'] if mix else []))]
+                     + ([pre + 'to_value_residual_mix.0.weight'] if mix else [])
+                     + ([pre + 'to_v_head_gate.weight'] if c.gate_value_heads else []))]
             bias = ([pre + 'to_v_gate.bias'] if c.gate_values else []) + \
-                   ([pre + 'to_value_residual_mix.0.bias'] if mix else [])
+                   ([pre + 'to_value_residual_mix.0.bias'] if mix else []) + \
+                   ([pre + 'to_v_head_gate.bias'] if c.gate_value_heads else [])
             if bias:
                 g.append(grp(bias))
             g += [grp([n]) for n in params if n not in taken and (n.startswith(pa) or n.startswith(pf))]
@@ -317,9 +327,14 @@ class WorldModelActorCritic(nn.Module):
             wn = [pre + 'to_q.weight', pre + 'to_k.weight', pre + 'to_v.weight']
             wn += [pre + 'to_v_gate.weight'] if c.gate_values else []
             wn += [pre + 'to_value_residual_mix.0.weight'] if mix else []
-            bn = ([pre + 'to_v_gate.bias'] if c.gate_values else []) + ([pre + 'to_value_residual_mix.0.bias'] if mix else [])
-            n_out = I + 2 * c.kv_inner + (I if c.gate_values else 0) + (c.n_kv_heads if mix else 0)
+            wn += [pre + 'to_v_head_gate.weight'] if c.gate_value_heads else []
+            bn = ([pre + 'to_v_gate.bias'] if c.gate_values else []) + ([pre + 'to_value_residual_mix.0.bias'] if mix else []) \
+                + ([pre + 'to_v_head_gate.bias'] if c.gate_value_heads else [])
+            # q | k | v | gate | mix | head gate: the head gates come last, so every earlier column keeps its offset
+            mix_col = I + 2 * c.kv_inner + (I if c.gate_values else 0)
+            n_out = mix_col + (c.n_kv_heads if mix else 0) + (c.heads if c.gate_value_heads else 0)
             entry = dict(w=flat.span(wn).view(n_out, d), wg=flat.span(wn, flat.grad).view(n_out, d), mix=mix,
+                         mix_col=mix_col, hg_col=n_out - c.heads if c.gate_value_heads else -1,
                          b=flat.span(bn) if bn else None, bg=flat.span(bn, flat.grad) if bn else None)
             self._proj.append(entry)
         hn = ['action_head.0.weight', 'critic_head.0.weight']
@@ -363,7 +378,7 @@ class WorldModelActorCritic(nn.Module):
             (ln_a, _, _), blk, _ = attn_l
             xn = ln_a(x)
             P = self._proj[li]
-            # one projection for q | k | v | gate | mix: one well-shaped GEMM, gradient into the flat buffer
+            # one projection for q | k | v | gate | mix | head gate: one well-shaped GEMM, gradient into the flat buffer
             bias = None
             if P['b'] is not None:
                 bias = torch.cat((self._zero_bias(nq3, x), P['b']))
@@ -373,7 +388,7 @@ class WorldModelActorCritic(nn.Module):
             gate_pre = proj[..., nq3:nq3 + I] if c.gate_values else None
             orig_v = v
             if P['mix'] and first_v is not None:
-                mix = torch.sigmoid(proj[..., -Hkv:]).permute(0, 2, 1)[..., None]
+                mix = torch.sigmoid(proj[..., P['mix_col']:P['mix_col'] + Hkv]).permute(0, 2, 1)[..., None]
                 v = v.lerp(first_v, mix)
             if first_v is None:
                 first_v = orig_v
@@ -384,6 +399,8 @@ class WorldModelActorCritic(nn.Module):
             o = ops.attention(q, k, v, lens, scale, p_drop, attn_seed, attn_offset, li, window=c.attn_window,
                               mem_k=getattr(blk, 'mem_k', None), mem_v=getattr(blk, 'mem_v', None),
                               add_zero_kv=c.add_zero_kv, alibi_slopes=self.alibi_slopes, softclamp=c.softclamp)
+            if c.gate_value_heads:   # per-head output gate, before the heads are merged: [b, n, H] -> [b, H, n, 1]
+                o = o * proj[..., P['hg_col']:P['hg_col'] + H].sigmoid().permute(0, 2, 1)[..., None]
             o = o.permute(0, 2, 1, 3).reshape(b, n, I)
             if gate_pre is not None:
                 o = o * gate_pre.sigmoid()

@@ -48,7 +48,9 @@ class RolloutEngine:
         # grouped-query attention (Agent kv_heads / world_model['attn_one_kv_head']): k, v, the mix and the caches have Hkv heads
         Hkv = self.Hkv = int(getattr(c, 'kv_heads', 0) or H)
         Ikv = Hkv * dh
-        self.n_qkv = I + 2 * Ikv + (I if c.gate_values else 0) + (Hkv if (c.value_residual and c.learned_mix) else 0)
+        head_gate = bool(getattr(c, 'gate_value_heads', False))   # per-head output gates: the row's last H columns
+        self.n_qkv = I + 2 * Ikv + (I if c.gate_values else 0) + (Hkv if (c.value_residual and c.learned_mix) else 0) \
+            + (H if head_gate else 0)
         ff = d * c.ff_mult
         nA = 2 * A if c.continuous else A
         f32, i32, u8 = torch.float32, torch.int32, torch.uint8
@@ -185,6 +187,7 @@ class RolloutEngine:
             self.alibi_slopes = ops.alibi_slopes(c.heads, c.alibi_heads).to(self.dev)
             D.alibi_slopes = self.alibi_slopes.data_ptr()
         D.attn_softclamp = float(getattr(c, 'softclamp', 0.))   # logit soft-clamp value (0: off)
+        D.head_gate = int(bool(getattr(c, 'gate_value_heads', False)))   # per-head output gates
         D.sim_mode, D.hazard_log2, D.rs_eps = self.sim_mode, hazard_log2, 1e-5
         if clamp is not None:
             D.clamp_lo, D.clamp_hi, D.has_clamp = float(clamp[0]), float(clamp[1]), 1
@@ -243,6 +246,11 @@ class RolloutEngine:
                 else:   # first layer: columns present but unused
                     rows.append(torch.zeros(self.Hkv, c.dim, device=self.dev))
                     bias.append(torch.zeros(self.Hkv, device=self.dev))
+            if getattr(blk, 'to_v_head_gate', None) is not None:
+                rows.append(blk.to_v_head_gate.weight)
+                bias.append(blk.to_v_head_gate.bias)
+            elif getattr(c, 'gate_value_heads', False):
+                raise RuntimeError('gate_value_heads set but layer has no to_v_head_gate')
             torch.cat(rows, out=wl['w_qkv'])
             torch.cat(bias, out=wl['b_qkv'][:self.n_qkv])
             if 'mem_k' in wl:   # attention sinks

@@ -144,20 +144,24 @@ class FusedTrainStep:
         X = [E(T, d) for _ in range(L_ + 1)]
         max_qkv = 0
         nw = 'g' if c.rms_norm else 'gamma'   # x-transformers RMSNorm.g / LayerNorm.gamma
+        head_gate = bool(getattr(c, 'gate_value_heads', False))   # per-head output gates: H more projection columns
         for li in range(L_):
             mix = bool(c.value_residual and c.learned_mix and li > 0)
             pa, pf = f'{pre}{2 * li}.', f'{pre}{2 * li + 1}.'
             wn = [pa + '1.to_q.weight', pa + '1.to_k.weight', pa + '1.to_v.weight']
             wn += [pa + '1.to_v_gate.weight'] if c.gate_values else []
             wn += [pa + '1.to_value_residual_mix.0.weight'] if mix else []
+            wn += [pa + '1.to_v_head_gate.weight'] if head_gate else []
             bn = ([pa + '1.to_v_gate.bias'] if c.gate_values else []) + \
-                 ([pa + '1.to_value_residual_mix.0.bias'] if mix else [])
-            n_qkv = I + 2 * Ikv + (I if c.gate_values else 0) + (c.n_kv_heads if mix else 0)   # q | k | v | gate | mix
+                 ([pa + '1.to_value_residual_mix.0.bias'] if mix else []) + \
+                 ([pa + '1.to_v_head_gate.bias'] if head_gate else [])
+            # q | k | v | gate | mix | head gate
+            n_qkv = I + 2 * Ikv + (I if c.gate_values else 0) + (c.n_kv_heads if mix else 0) + (H if head_gate else 0)
             max_qkv = max(max_qkv, n_qkv)
             bufs = dict(x_attn=X[li], x_ff=E(T, d), xn_attn=E(T, d), xn_ff=E(T, d), st_attn=E(T, 2), st_ff=E(T, 2),
                         proj=E(T, n_qkv), qkv=E(T, I + 2 * Ikv), o=E(T, I), lse=E(b_max * H * n_max), u=E(T, lu2),
                         hd=E(T, lff))
-            bufs['og'] = E(T, I) if c.gate_values else bufs['o']
+            bufs['og'] = E(T, I) if (c.gate_values or head_gate) else bufs['o']   # (either gate: a buffer of its own)
             self.layers_py.append(bufs)
             Ly = layers[li]
             Ly.ln_attn, Ly.w_proj = off(pa + '0.0.' + nw), span_off(wn)
@@ -216,6 +220,7 @@ class FusedTrainStep:
             self.alibi_slopes = ops.alibi_slopes(H, c.alibi_heads).to(dev)
             D.alibi_slopes = self.alibi_slopes.data_ptr()
         D.attn_softclamp = float(getattr(c, 'softclamp', 0.))   # logit soft-clamp value (0: off)
+        D.head_gate = int(head_gate)
         D.inv_freq = self.inv_freq.data_ptr()
         for k, t in self.buf.items():
             setattr(D, k, t.data_ptr())
